@@ -76,7 +76,13 @@ def parse():
                         "refinement loop at one fp16 MFMA product per block.  A SEPARATE line, never the headline")
     p.add_argument("--conv-backend", default=None, choices=["f16x3", "f16x2", "f16", "miopen"],
                    help="update-block convolution path (default: the package default, f16x3)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned (flow_lo, flow_up) to DIR/<name>.npy as float32, at most 64 MB "
+                        "in all (a fixed seeded sample of each array beyond that); inputs and weights are seeded, so two builds "
+                        "run with the same arguments can be compared output for output")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     if a.batch is None:
         a.batch = 8 if a.gpus > 1 else 1
     return a
@@ -123,6 +129,30 @@ def pmc_traffic(args):
                 "lookup_operator_bytes": j.get("lookup_operator_bytes"), "note": "measured in this run: %s" % j.get("source")}
     except Exception as e:          # counters unavailable on this box: say so, report nothing
         return {"note": "--pmc failed: %s" % (str(e)[:200],)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes {name: float32 array} to path/<name>.npy.  When the arrays together exceed `limit` bytes, each is replaced by
+    the same fraction of its elements: a sorted sample of flat indices drawn with a fixed seed, so the sample depends only on
+    the array's shape.  Returns {name: {"shape", "saved_elements"}} for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = limit - 4096 * len(arrays)                 # (room for the .npy headers)
+    keep = min(1.0, budget / total) if total else 1.0
+    info = {}
+    for name, a in arrays.items():
+        flat = a
+        if keep < 1.0:
+            k = int(a.size * keep)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            flat = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(flat, dtype=np.float32))
+        info[name] = {"shape": list(a.shape), "saved_elements": int(flat.size)}
+    return info
 
 
 def conv_precision(dev):
@@ -236,10 +266,10 @@ def main():
         return make
 
     def step():
-        _, up = model(i1, i2, iters=args.iters, test_mode=True)
+        lo, up = model(i1, i2, iters=args.iters, test_mode=True)
         if world > 1:
             up = gather_disparity(up, B * world, dst=0)
-        return up
+        return lo, up
 
     def sync():
         if world > 1:
@@ -259,10 +289,15 @@ def main():
         model.check_finite = False          # no host sync per forward inside the timed region: checked once behind it
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            last = step()
+            last_lo, last = step()
         sync()
         t1 = time.perf_counter()
         model.check_finite = True
+        # what the last timed step returned, copied before any later forward can reuse the loop's buffers (flow_up holds every
+        # rank's pairs on rank 0, flow_lo rank 0's own)
+        dumped = None
+        if args.dump_outputs and rank == 0:
+            dumped = {"flow_lo": last_lo.float().cpu().numpy(), "flow_up": last.float().cpu().numpy()}
         gathered_batch = int(last.shape[0]) if last is not None else None      # (rank 0 holds all ranks' maps)
         # the timed region ran without the per-forward check (no host synchronisation inside it): its post-conditions are read
         # ONCE behind it -- the error word of the fused ConvGRU / chain launches (a time-out inside the region must not be
@@ -720,6 +755,8 @@ def main():
             out["reference_fixture"] = "unavailable: %s" % e
     if not args.skip_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, sd, dict(BASE_CONFIG), i1, i2)
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dumped)}
     print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -67,7 +67,9 @@ def build(force=False, verbose=False):
         return job, subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
 
     from concurrent.futures import ThreadPoolExecutor
-    workers = max(1, min(len(jobs), int(os.environ.get("DKT_BUILD_JOBS", os.cpu_count() or 4))))
+    # (os.cpu_count() is the whole host's count, not what this process may use: MAX_JOBS when set, else at most 16)
+    workers = int(os.environ.get("DKT_BUILD_JOBS") or os.environ.get("MAX_JOBS") or min(os.cpu_count() or 4, 16))
+    workers = max(1, min(len(jobs), workers))
     with ThreadPoolExecutor(workers) as pool:
         results = list(pool.map(compile_one, jobs))
     for (src, obj, extra), res in results:
