@@ -157,6 +157,9 @@ SIGNATURES = {
     "dkt_gwc_volume": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _l, _i, _vp],
     "dkt_gwc_volume_mfma": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _l, _i, _vp],
     "dkt_concat_volume": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _l, _i, _vp],
+    "dkt_gwc_volume_bwd": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "dkt_concat_volume_bwd": [_vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "dkt_gwc_concat_volume_bwd": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_gru_gate_zr": [_vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _l, _i, _vp],
     "dkt_gru_gate_out": [_vp, _vp, _l, _vp, _vp, _l, _vp, _l, _i, _i, _l, _i, _vp],
     "dkt_conv2d_packed_elems": [_ip, _i, _i, _i, _i],

@@ -8,6 +8,9 @@ so the reference's checkpoints load with ``strict=True``.  Like the reference's 
 pointed at ``dkt_stereo_amd.submodule`` for its volumes; this class exists so that the whole path runs, is
 timed and is parity-checked where the reference is not present.
 
+Training (``train()``, gwc_main.py:279-326 minus ptrans / autocast) runs the same volume kernels as autograd
+nodes (backward: volumes_bwd.hip); the 2-D and 3-D layers are torch with batch-statistics BatchNorm.
+
 What runs where (inference, ``test_mode=True``):
   * 2-D feature extraction: every 3x3 / 1x1 convolution with its eval-mode BatchNorm folded in runs on
     dkt_conv2d_f16s[_strided]; the dilated layer4 stays on the vendor library;
@@ -194,10 +197,24 @@ class GWCNet(nn.Module):
     def freeze_bn(self):
         pass
 
+    def _predict(self, classif, out):
+        """classif -> x4 trilinear -> softmax -> soft-argmin, negated: gwc_main.py:250-268."""
+        cost = classif[2](_cbn3(classif[0], out, True))
+        cost = F.interpolate(cost, scale_factor=4, mode='trilinear', align_corners=False)
+        pred = F.softmax(torch.squeeze(cost, 1), dim=1)
+        return -disparity_regression(pred, self.maxdisp).unsqueeze(1)
+
     def cost_regularization(self, cost):
-        """gwc_main.py:234-277, eval branch: only the last classifier contributes to the result."""
+        """gwc_main.py:234-277.  Eval: only the last classifier contributes to the result.  Training: the four
+        predictions [-pred0, -pred1, -pred2, -pred3] of classif0..3 (each (B,1,H,W))."""
         c0 = _cbn3(self.dres0[2], _cbn3(self.dres0[0], cost, True), True)
         c0 = _cbn3(self.dres1[2], _cbn3(self.dres1[0], c0, True)) + c0
+        if self.training:
+            out1 = self.dres2(c0)
+            out2 = self.dres3(out1)
+            out3 = self.dres4(out2)
+            return [self._predict(self.classif0, c0), self._predict(self.classif1, out1),
+                    self._predict(self.classif2, out2), self._predict(self.classif3, out3)]
         out3 = self.dres4(self.dres3(self.dres2(c0)))
         cost3 = self.classif3[2](_cbn3(self.classif3[0], out3, True))
         cost3 = F.interpolate(cost3, scale_factor=4, mode='trilinear', align_corners=False)
@@ -212,10 +229,32 @@ class GWCNet(nn.Module):
                                            featL["concat_feature"], featR["concat_feature"], d, self.num_groups)
         return build_gwc_volume(featL["gwc_feature"], featR["gwc_feature"], d, self.num_groups)
 
-    @torch.no_grad()
     def forward(self, imgL, imgR, iters=None, flow_init=None, test_mode=False):
-        if not test_mode or self.training:
-            raise NotImplementedError("dkt_stereo_amd.GWCNet is the inference path (eval(), test_mode=True)")
+        """gwc_main.py:279-326 without ptrans and autocast (fp32).  test_mode=True -> (None, dispEsts), else
+        {"disp_preds": dispEsts}; dispEsts is the list of four predictions in training, the final one in eval.
+        Training runs under autograd: the volume builders' backward (volumes_bwd.hip) carries the gradient into
+        feature_extraction, whose BatchNorms use batch statistics and update their running statistics."""
+        if test_mode and not self.training:
+            return self._infer(imgL, imgR)
+        imgL = (2 * (imgL / 255.0) - 1.0).contiguous()
+        imgR = (2 * (imgR / 255.0) - 1.0).contiguous()
+        if self.training:
+            # two calls as in the reference (gwc_main.py:302-303): each image's batch has its own BN statistics
+            featL = self.feature_extraction(imgL)
+            featR = self.feature_extraction(imgR)
+        else:
+            B = imgL.shape[0]
+            feats = self.feature_extraction(torch.cat([imgL, imgR], 0))
+            featL = {k: v[:B] for k, v in feats.items()}
+            featR = {k: v[B:] for k, v in feats.items()}
+        disp_ests = self.cost_regularization(self.build_volume(featL, featR))
+        if test_mode:
+            return None, disp_ests
+        return {"disp_preds": disp_ests}
+
+    @torch.no_grad()
+    def _infer(self, imgL, imgR):
+        """eval(), test_mode=True: the inference path."""
         imgL = (2 * (imgL / 255.0) - 1.0).contiguous()
         imgR = (2 * (imgR / 255.0) - 1.0).contiguous()
         # both images through the shared-weight extractor as one batch of two

@@ -10,6 +10,10 @@ definitions that differ in the reference half; both are here:
 
 ``build_gwc_concat_volume`` writes both into one (B, G+2C', D, H, W) buffer,
 replacing the torch.cat of gwc_main.py:315.
+
+These four builders are differentiable: with grad enabled and an input that requires grad the same forward
+kernels run inside a ``torch.autograd.Function`` whose backward is dkt_gwc_volume_bwd / dkt_concat_volume_bwd /
+dkt_gwc_concat_volume_bwd (volumes_bwd.hip).  Otherwise nothing changes: the plain call, the same bits.
 """
 import torch
 
@@ -18,7 +22,6 @@ from . import _ffi
 
 def _check_pair(ref, tgt):
     _ffi.require_gpu(ref, tgt)
-    _ffi.require_no_grad(ref, tgt)
     if ref.shape != tgt.shape:
         raise ValueError("feature maps disagree: %s vs %s" % (tuple(ref.shape), tuple(tgt.shape)))
     return ref.contiguous(), tgt.contiguous()
@@ -69,35 +72,21 @@ def _concat_into(ref, tgt, vol, maxdisp, ref_masked, bstride):
     _ffi.check(rc, "dkt_concat_volume")
 
 
-def build_gwc_volume(refimg_fea, targetimg_fea, maxdisp, num_groups):
-    ref, tgt = _check_pair(refimg_fea, targetimg_fea)
+def _gwc_volume(ref, tgt, maxdisp, num_groups):
     B, C, H, W = ref.shape
     vol = torch.empty((B, num_groups, maxdisp, H, W), device=ref.device, dtype=torch.float32)
     _gwc_into(ref, tgt, vol, maxdisp, num_groups, num_groups * maxdisp * H * W)
     return vol
 
 
-def build_concat_volume(refimg_fea, targetimg_fea, maxdisp):
-    ref, tgt = _check_pair(refimg_fea, targetimg_fea)
+def _concat_volume(ref, tgt, maxdisp, ref_masked):
     B, C, H, W = ref.shape
     vol = torch.empty((B, 2 * C, maxdisp, H, W), device=ref.device, dtype=torch.float32)
-    _concat_into(ref, tgt, vol, maxdisp, True, 2 * C * maxdisp * H * W)
+    _concat_into(ref, tgt, vol, maxdisp, ref_masked, 2 * C * maxdisp * H * W)
     return vol
 
 
-def build_concat_volume_igev(refimg_fea, targetimg_fea, maxdisp):
-    ref, tgt = _check_pair(refimg_fea, targetimg_fea)
-    B, C, H, W = ref.shape
-    vol = torch.empty((B, 2 * C, maxdisp, H, W), device=ref.device, dtype=torch.float32)
-    _concat_into(ref, tgt, vol, maxdisp, False, 2 * C * maxdisp * H * W)
-    return vol
-
-
-def build_gwc_concat_volume(gwc_ref, gwc_tgt, cat_ref, cat_tgt, maxdisp, num_groups):
-    """GWCNet.forward with use_concat_volume (gwc_main.py:310-315) in one buffer:
-    channels [0:G] group-wise correlation, [G:G+2C'] concat volume."""
-    gref, gtgt = _check_pair(gwc_ref, gwc_tgt)
-    cref, ctgt = _check_pair(cat_ref, cat_tgt)
+def _gwc_concat_volume(gref, gtgt, cref, ctgt, maxdisp, num_groups):
     B, _, H, W = gref.shape
     Cc = cref.shape[1]
     ch = num_groups + 2 * Cc
@@ -106,6 +95,139 @@ def build_gwc_concat_volume(gwc_ref, gwc_tgt, cat_ref, cat_tgt, maxdisp, num_gro
     _gwc_into(gref, gtgt, vol, maxdisp, num_groups, bstride)
     _concat_into(cref, ctgt, vol[:, num_groups:], maxdisp, True, bstride)
     return vol
+
+
+def _grad_operand(g):
+    """(tensor, batch stride) of an upstream gradient: read in place when only its batch stride is unusual
+    (a batch-sliced view), else made contiguous."""
+    g = g.float()
+    B, ch, D, H, W = g.shape
+    if g.stride()[1:] != (D * H * W, H * W, W, 1) or (B > 1 and g.stride(0) < ch * D * H * W):
+        g = g.contiguous()
+    return g, g.stride(0) if B > 1 else ch * D * H * W
+
+
+def _needs_autograd(*tensors):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in tensors)
+
+
+def _empty_or_none(need, like):
+    return torch.empty_like(like) if need else None
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+class _GwcFn(torch.autograd.Function):
+    """build_gwc_volume; backward dkt_gwc_volume_bwd."""
+
+    @staticmethod
+    def forward(ctx, ref, tgt, maxdisp, num_groups):
+        ctx.meta = (maxdisp, num_groups)
+        ctx.save_for_backward(ref, tgt)
+        return _gwc_volume(ref, tgt, maxdisp, num_groups)
+
+    @staticmethod
+    def backward(ctx, gvol):
+        ref, tgt = ctx.saved_tensors
+        D, G = ctx.meta
+        B, C, H, W = ref.shape
+        gv, bstride = _grad_operand(gvol)
+        gr = _empty_or_none(ctx.needs_input_grad[0], ref)
+        gt = _empty_or_none(ctx.needs_input_grad[1], tgt)
+        if gr is None and gt is None:
+            return None, None, None, None
+        rc = _ffi.lib().dkt_gwc_volume_bwd(gv.data_ptr(), bstride, ref.data_ptr(), tgt.data_ptr(), _ptr(gr), _ptr(gt),
+                                           B, C, H, W, D, G, _ffi.device_of(ref), _ffi.stream_of(ref))
+        _ffi.check(rc, "dkt_gwc_volume_bwd")
+        return gr, gt, None, None
+
+
+class _ConcatFn(torch.autograd.Function):
+    """build_concat_volume[_igev]; backward dkt_concat_volume_bwd (needs no saved feature maps)."""
+
+    @staticmethod
+    def forward(ctx, ref, tgt, maxdisp, ref_masked):
+        ctx.meta = (maxdisp, ref_masked)
+        ctx.shape = tuple(ref.shape)
+        return _concat_volume(ref, tgt, maxdisp, ref_masked)
+
+    @staticmethod
+    def backward(ctx, gvol):
+        D, ref_masked = ctx.meta
+        B, C, H, W = ctx.shape
+        gv, bstride = _grad_operand(gvol)
+        mk = lambda need: torch.empty(ctx.shape, device=gv.device, dtype=torch.float32) if need else None  # noqa: E731
+        gr, gt = mk(ctx.needs_input_grad[0]), mk(ctx.needs_input_grad[1])
+        if gr is None and gt is None:
+            return None, None, None, None
+        rc = _ffi.lib().dkt_concat_volume_bwd(gv.data_ptr(), bstride, _ptr(gr), _ptr(gt), B, C, H, W, D, int(ref_masked),
+                                              _ffi.device_of(gv), _ffi.stream_of(gv))
+        _ffi.check(rc, "dkt_concat_volume_bwd")
+        return gr, gt, None, None
+
+
+class _GwcConcatFn(torch.autograd.Function):
+    """build_gwc_concat_volume; backward: both channel ranges of the buffer's gradient in ONE launch
+    (dkt_gwc_concat_volume_bwd), read in place."""
+
+    @staticmethod
+    def forward(ctx, gref, gtgt, cref, ctgt, maxdisp, num_groups):
+        ctx.meta = (maxdisp, num_groups)
+        ctx.cat_shape = tuple(cref.shape)
+        ctx.save_for_backward(gref, gtgt)
+        return _gwc_concat_volume(gref, gtgt, cref, ctgt, maxdisp, num_groups)
+
+    @staticmethod
+    def backward(ctx, gvol):
+        gref, gtgt = ctx.saved_tensors
+        D, G = ctx.meta
+        B, C, H, W = gref.shape
+        Cc = ctx.cat_shape[1]
+        gv, bstride = _grad_operand(gvol)
+        need = ctx.needs_input_grad
+        gr, gt = _empty_or_none(need[0], gref), _empty_or_none(need[1], gtgt)
+        mk = lambda n: torch.empty(ctx.cat_shape, device=gv.device, dtype=torch.float32) if n else None  # noqa: E731
+        cr, ct = mk(need[2]), mk(need[3])
+        if gr is None and gt is None and cr is None and ct is None:
+            return None, None, None, None, None, None
+        rc = _ffi.lib().dkt_gwc_concat_volume_bwd(gv.data_ptr(), bstride, gref.data_ptr(), gtgt.data_ptr(), _ptr(gr), _ptr(gt),
+                                                  B, C, G, _ptr(cr), _ptr(ct), Cc, 1, H, W, D,
+                                                  _ffi.device_of(gv), _ffi.stream_of(gv))
+        _ffi.check(rc, "dkt_gwc_concat_volume_bwd")
+        return gr, gt, cr, ct, None, None
+
+
+def build_gwc_volume(refimg_fea, targetimg_fea, maxdisp, num_groups):
+    ref, tgt = _check_pair(refimg_fea, targetimg_fea)
+    if _needs_autograd(ref, tgt):
+        return _GwcFn.apply(ref, tgt, maxdisp, num_groups)
+    return _gwc_volume(ref, tgt, maxdisp, num_groups)
+
+
+def build_concat_volume(refimg_fea, targetimg_fea, maxdisp):
+    ref, tgt = _check_pair(refimg_fea, targetimg_fea)
+    if _needs_autograd(ref, tgt):
+        return _ConcatFn.apply(ref, tgt, maxdisp, True)
+    return _concat_volume(ref, tgt, maxdisp, True)
+
+
+def build_concat_volume_igev(refimg_fea, targetimg_fea, maxdisp):
+    ref, tgt = _check_pair(refimg_fea, targetimg_fea)
+    if _needs_autograd(ref, tgt):
+        return _ConcatFn.apply(ref, tgt, maxdisp, False)
+    return _concat_volume(ref, tgt, maxdisp, False)
+
+
+def build_gwc_concat_volume(gwc_ref, gwc_tgt, cat_ref, cat_tgt, maxdisp, num_groups):
+    """GWCNet.forward with use_concat_volume (gwc_main.py:310-315) in one buffer:
+    channels [0:G] group-wise correlation, [G:G+2C'] concat volume."""
+    gref, gtgt = _check_pair(gwc_ref, gwc_tgt)
+    cref, ctgt = _check_pair(cat_ref, cat_tgt)
+    if _needs_autograd(gref, gtgt, cref, ctgt):
+        return _GwcConcatFn.apply(gref, gtgt, cref, ctgt, maxdisp, num_groups)
+    return _gwc_concat_volume(gref, gtgt, cref, ctgt, maxdisp, num_groups)
 
 
 def _group_l2norm(x, num_groups):
@@ -127,13 +249,15 @@ def build_gwc_volume_norm(refimg_fea, targetimg_fea, maxdisp, num_groups):
     """meta_arch/cgi/submodule.py:154-164: group-wise correlation of features normalised per
     channel group.  The norm reduces over channels only, so normalising the two maps once and
     running the plain group-wise volume is the same computation as the reference's per-
-    disparity slices."""
+    disparity slices.  Inference only: inputs that require grad are refused (the normalisation has no
+    backward here; CGI is not trainable on this library)."""
     return build_gwc_volume(_group_l2norm(refimg_fea, num_groups), _group_l2norm(targetimg_fea, num_groups),
                             maxdisp, num_groups)
 
 
 def build_norm_correlation_volume(refimg_fea, targetimg_fea, maxdisp):
-    """meta_arch/cgi/submodule.py:171-180 (== igev_stereo/submodule.py:179): (B,1,D,H,W)."""
+    """meta_arch/cgi/submodule.py:171-180 (== igev_stereo/submodule.py:179): (B,1,D,H,W).  Inference only, like
+    build_gwc_volume_norm."""
     return build_gwc_volume_norm(refimg_fea, targetimg_fea, maxdisp, 1)
 
 

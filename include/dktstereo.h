@@ -211,6 +211,34 @@ int dkt_concat_volume(const float *ref, const float *tgt, float *vol,
                       int B, int C, int H, int W, int D, int ref_masked, long vol_bstride,
                       int device, void *stream);
 
+/* Backward of dkt_gwc_volume: torch autograd through build_gwc_volume's per-disparity slices
+ * (meta_arch/igev_stereo/submodule.py:152-170 == meta_arch/gwcnet/submodules.py:39-58).
+ *   grad_ref[b,gc,h,w]  = (1/cpg) sum_{d <= w, d < D}   grad_vol[b,g,d,h,w]    * tgt[b,gc,h,w-d]
+ *   grad_tgt[b,gc,h,w'] = (1/cpg) sum_{d < D, w'+d < W} grad_vol[b,g,d,h,w'+d] * ref[b,gc,h,w'+d]
+ * grad_vol: (B,G,D,H,W) with batch stride vol_bstride (the gwc part of the fused buffer is read in place).
+ * grad_ref / grad_tgt: (B,C,H,W), overwritten; either may be null (not both).  Deterministic: no atomics,
+ * each element summed by one thread in ascending d. */
+int dkt_gwc_volume_bwd(const float *grad_vol, long vol_bstride, const float *ref, const float *tgt,
+                       float *grad_ref, float *grad_tgt, int B, int C, int H, int W, int D, int G,
+                       int device, void *stream);
+
+/* Backward of dkt_concat_volume (a banded sum of grad_vol over d):
+ * ref_masked = 1: meta_arch/gwcnet/submodules.py:25-36   grad_ref[c,w] = sum_{d <= w, d < D} grad_vol[c,d,w]
+ * ref_masked = 0: meta_arch/igev_stereo/submodule.py:207-218  grad_ref[c,w] = sum_{d < D} grad_vol[c,d,w]
+ * both:  grad_tgt[c,w'] = sum_{d < D, w'+d < W} grad_vol[C+c,d,w'+d]        (h and b implied)
+ * grad_vol: (B,2C,D,H,W) with batch stride vol_bstride.  Either output may be null (not both). */
+int dkt_concat_volume_bwd(const float *grad_vol, long vol_bstride, float *grad_ref, float *grad_tgt,
+                          int B, int C, int H, int W, int D, int ref_masked, int device, void *stream);
+
+/* Both parts of the fused (B, G+2Cc, D, H, W) buffer of dkt_gwc_volume + dkt_concat_volume (the backward of
+ * gwc_main.py:310-315's torch.cat): channels [0,G) as dkt_gwc_volume_bwd (ref, tgt: (B,C,H,W)), channels
+ * [G, G+2Cc) as dkt_concat_volume_bwd (grad_cat_*: (B,Cc,H,W)), in one launch.  Any one of the four outputs
+ * may be null; ref / tgt only matter when a gwc gradient is requested. */
+int dkt_gwc_concat_volume_bwd(const float *grad_vol, long vol_bstride, const float *ref, const float *tgt,
+                              float *grad_ref, float *grad_tgt, int B, int C, int G,
+                              float *grad_cat_ref, float *grad_cat_tgt, int Cc, int ref_masked,
+                              int H, int W, int D, int device, void *stream);
+
 /* ---- ConvGRU gate fusions ---------------------------------------------------- */
 
 /* First gate stage of ConvGRU.forward (core/update.py:27-29 ==

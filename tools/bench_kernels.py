@@ -4,7 +4,7 @@ is HIP-event time over N back-to-back launches on torch's current stream
 (the stream handed to the C ABI), reported per launch together with the
 algorithmic bytes / flops of SURVEY.md section 8d.
 
-    python tools/bench_kernels.py [lookup] [build] [gates] [conv] [e2e] [autocast] [volumes]
+    python tools/bench_kernels.py [lookup] [build] [gates] [conv] [e2e] [autocast] [volumes] [volumes_bwd]
 """
 import json
 import os
@@ -312,6 +312,50 @@ def bench_volumes():
     report("geo_lookup + convc1 fused -> C8S (random)", timeit(lambda: fn.lookup_conv1x1(disp, coords, c1, out_c8=dst), n=50), bytes_=184 * 312 * (728 + 256))
 
 
+def bench_volumes_bwd():
+    """Backward of the GwcNet cfg5 volumes (544x960 input: C = 320, G = 40, D = 48, H = 136, W = 240 + the 12-channel
+    concat volume), straight through the C ABI.  Compulsory traffic: the upstream gradient (gwc 250.7 MB + concat
+    150.4 MB), the gwc feature maps read (83.6 MB) and all four feature gradients written (86.7 MB): 571.4 MB, 71 us at
+    8 TB/s.  The concat part needs no feature maps."""
+    from dkt_stereo_amd import _ffi
+    L = _ffi.lib()
+    B, C, Cc, G, D, H, W = 1, 320, 12, 40, 48, 136, 240
+    ch = G + 2 * Cc
+    gv = torch.randn(B, ch, D, H, W, device=DEV)
+    a, b = (torch.randn(B, C, H, W, device=DEV) for _ in range(2))
+    ga, gb = torch.empty_like(a), torch.empty_like(b)
+    gca, gcb = (torch.empty(B, Cc, H, W, device=DEV) for _ in range(2))
+    bs = ch * D * H * W
+    dv, st = _ffi.device_of(gv), lambda: _ffi.stream_of(gv)
+    gv_c = gv[:, G:]
+
+    def fused():
+        _ffi.check(L.dkt_gwc_concat_volume_bwd(gv.data_ptr(), bs, a.data_ptr(), b.data_ptr(), ga.data_ptr(), gb.data_ptr(), B, C, G,
+                                               gca.data_ptr(), gcb.data_ptr(), Cc, 1, H, W, D, dv, st()), "bwd")
+
+    def gwc():
+        _ffi.check(L.dkt_gwc_volume_bwd(gv.data_ptr(), bs, a.data_ptr(), b.data_ptr(), ga.data_ptr(), gb.data_ptr(),
+                                        B, C, H, W, D, G, dv, st()), "bwd")
+
+    def cat():
+        _ffi.check(L.dkt_concat_volume_bwd(gv_c.data_ptr(), bs, gca.data_ptr(), gcb.data_ptr(), B, Cc, H, W, D, 1, dv, st()), "bwd")
+
+    f4 = 4
+    gwc_bytes = G * D * H * W * f4 + 4 * C * H * W * f4
+    cat_bytes = 2 * Cc * D * H * W * f4 + 2 * Cc * H * W * f4
+    print("compulsory traffic: gwc %.1f MB, concat %.1f MB, fused %.1f MB (roofline %.1f us at 8 TB/s)"
+          % (gwc_bytes / 1e6, cat_bytes / 1e6, (gwc_bytes + cat_bytes) / 1e6, (gwc_bytes + cat_bytes) / 8e6))
+    # eager back-to-back launches: each is ~100 us, far above the launch cost
+    report("volumes_bwd fused gwc+concat cfg5", timeit(fused, n=50, graph=False), bytes_=gwc_bytes + cat_bytes)
+    report("volumes_bwd gwc only cfg5", timeit(gwc, n=50, graph=False), bytes_=gwc_bytes)
+    report("volumes_bwd concat only cfg5", timeit(cat, n=50, graph=False), bytes_=cat_bytes)
+    from dkt_stereo_amd.submodule import build_gwc_concat_volume
+    fwd_in = [t.clone() for t in (a, b)] + [torch.randn(B, Cc, H, W, device=DEV) for _ in range(2)]
+    with torch.no_grad():
+        report("volumes fwd fused gwc+concat cfg5 (for scale)", timeit(lambda: build_gwc_concat_volume(*fwd_in, D, G), n=50, graph=False),
+               bytes_=2 * C * H * W * f4 + 2 * Cc * H * W * f4 + ch * D * H * W * f4)
+
+
 def bench_next():
     """SURVEY 8f rows at cfg2 / cfg3 sizes: PCVNet lookup, CGI normalised volume, lookup / pyramid
     backward, fused convex up-sampling (vs the torch op sequence)."""
@@ -471,7 +515,7 @@ def bench_c8():
 def main():
     which = sys.argv[1:] or ["lookup", "build", "gates", "conv", "e2e", "autocast", "volumes"]
     fns = dict(lookup=bench_lookup, build=bench_build, gates=bench_gates, conv=bench_conv, e2e=bench_e2e,
-               autocast=bench_autocast, volumes=bench_volumes, ablate=bench_ablate, next=bench_next, c8=bench_c8)
+               autocast=bench_autocast, volumes=bench_volumes, volumes_bwd=bench_volumes_bwd, ablate=bench_ablate, next=bench_next, c8=bench_c8)
     for w in which:
         print("== %s ==" % w, flush=True)
         try:
