@@ -185,6 +185,7 @@ SIGNATURES = {
     "dkt_instance_norm_workspace": [_i, _l],
     "dkt_instance_norm": [_vp, _vp, _vp, _i, _l, _f, _i, _i, _vp],
     "dkt_add_relu": [_vp, _vp, _vp, _l, _i, _vp],
+    "dkt_ema_update": [_vp, _vp, _vp, _i, _f, _f, _vp, _i, _vp],
     "dkt_pool2x": [_vp, _vp, _l, _i, _i, _i, _vp],
     "dkt_interp_bilinear": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }

@@ -169,6 +169,52 @@ def _packed_weights_locked(layer, src_channels):
     return p
 
 
+def _copy_unaliased(dst, src):
+    """dst <- src unless dst IS src's memory (a cached fp32 contiguous copy is often the parameter itself: writing it would
+    bump the parameter's version counter)."""
+    if dst.data_ptr() != src.data_ptr():
+        dst.copy_(src.detach())
+
+
+def _refresh_packed(layer, cache, R):
+    """ema.ema_update_: rewrite the current split-fp16 images of `layer` in place, same buffers and scales."""
+    L = _ffi.lib()
+    for slot, p in list(cache.items()):
+        if not R.current(p.key):
+            continue
+        w, b = layer.weight, layer.bias
+        src_channels = p.key[3]
+        n = len(src_channels)
+        ch = (ctypes.c_int * n)(*src_channels)
+        cout, _, kh, kw = w.shape
+        wc = w.detach().float().contiguous()
+        R.window(R.amax(w), p.inv_scale, lambda c=cache, s=slot, q=p: c.pop(s) if c.get(s) is q else None)
+        rc = L.dkt_conv2d_pack_weights(wc.data_ptr(), ch, n, cout, kh, kw, 1.0 / p.inv_scale, p.hi.data_ptr(), p.lo.data_ptr(),
+                                       _ffi.device_of(w), _ffi.stream_of(w))
+        _ffi.check(rc, "dkt_conv2d_pack_weights")
+        if p.bias is not None:
+            _copy_unaliased(p.bias, b)
+        p.key = R.rekey(p.key)
+
+
+def _refresh_stem7(layer, cache, R):
+    """ema.ema_update_: the 7x7 stem images of `layer` in place (see _stem7_packed)."""
+    L = _ffi.lib()
+    for slot, pk in list(cache.items()):
+        if not R.current(pk.key):
+            continue
+        w, b = layer.weight, layer.bias
+        cout, cin = w.shape[:2]
+        wc = w.detach().float().contiguous()
+        R.window(R.amax(w), pk.inv_scale, lambda c=cache, s=slot, q=pk: c.pop(s) if c.get(s) is q else None)
+        rc = L.dkt_conv2d_stem7_pack(wc.data_ptr(), cout, cin, 1.0 / pk.inv_scale, pk.hi.data_ptr(), pk.lo.data_ptr(),
+                                     _ffi.device_of(w), _ffi.stream_of(w))
+        _ffi.check(rc, "dkt_conv2d_stem7_pack")
+        if pk.bias is not None:
+            _copy_unaliased(pk.bias, b)
+        pk.key = R.rekey(pk.key)
+
+
 def clear_weight_cache(module):
     """Drops the packed fp16 weight images below `module` (needed only after writes
     that bypass the Parameter's version counter, e.g. ``weight.data.mul_()``)."""

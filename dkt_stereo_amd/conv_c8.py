@@ -11,7 +11,7 @@ import threading
 import torch
 
 from . import _ffi
-from .conv import _CACHE_LOCK
+from .conv import _CACHE_LOCK, _copy_unaliased
 
 
 def c8_dims(H, W):
@@ -248,6 +248,20 @@ class _PackedGru:
     __slots__ = ("key", "wzr", "wq", "inv_zr", "inv_q", "bz", "br", "bq")
 
 
+def _gru_images(gru, x_channels, hs, xs):
+    """(z|r weights interleaved in blocks of 32, q weights as [x... | r*h], hidden size) with the operand scales folded."""
+    wz, wr, wq = (p.detach().float() for p in (gru.convz.weight, gru.convr.weight, gru.convq.weight))
+    ch, cin = int(wz.shape[0]), int(wz.shape[1])
+    if ch != 128 or cin != ch + sum(x_channels):
+        raise ValueError("gru_c8: hidden size 128, operands of %d channels expected" % (cin - ch))
+    inv = _in_scale_vector([hs] + list(xs), wz.device)            # the reference's input order [h | x...] (= [r*h | x...])
+    if inv is not None:
+        wz, wr, wq = (w * inv.view(1, -1, 1, 1) for w in (wz, wr, wq))
+    wzr = torch.stack([wz.view(ch // 32, 32, cin, 3, 3), wr.view(ch // 32, 32, cin, 3, 3)], dim=1).reshape(2 * ch, cin, 3, 3)
+    wq2 = torch.cat([wq[:, ch:], wq[:, :ch]], dim=1)
+    return wzr, wq2, ch
+
+
 def gru_packed(gru, x_channels, h_scales=None, x_scales=None):
     """Weights of one ConvGRU (core/update.py:16-21) for dkt_gru_c8: the z|r image with its output channels interleaved in
     blocks of 32 (a wave holds z and r of the same hidden channels), the q image with its input channels reordered to
@@ -263,15 +277,7 @@ def gru_packed(gru, x_channels, h_scales=None, x_scales=None):
         hit = _cache_get(cache, slot, key)
         if hit is not None:
             return hit
-        wz, wr, wq = (p.detach().float() for p in ps[:3])
-        ch, cin = int(wz.shape[0]), int(wz.shape[1])
-        if ch != 128 or cin != ch + sum(x_channels):
-            raise ValueError("gru_c8: hidden size 128, operands of %d channels expected" % (cin - ch))
-        inv = _in_scale_vector([hs] + list(xs), wz.device)            # the reference's input order [h | x...] (= [r*h | x...])
-        if inv is not None:
-            wz, wr, wq = (w * inv.view(1, -1, 1, 1) for w in (wz, wr, wq))
-        wzr = torch.stack([wz.view(ch // 32, 32, cin, 3, 3), wr.view(ch // 32, 32, cin, 3, 3)], dim=1).reshape(2 * ch, cin, 3, 3)
-        wq2 = torch.cat([wq[:, ch:], wq[:, :ch]], dim=1)
+        wzr, wq2, ch = _gru_images(gru, x_channels, hs, xs)
         p = _PackedGru()
         p.wzr, p.inv_zr = _pack_raw(wzr, [ch] + list(x_channels))
         p.wq, p.inv_q = _pack_raw(wq2, list(x_channels) + [ch])
@@ -279,6 +285,74 @@ def gru_packed(gru, x_channels, h_scales=None, x_scales=None):
         p.key = key
         _cache_put(cache, slot, p, 6)
         return p
+
+
+def _repack_raw(w, src_channels, inv_scale, img):
+    """_pack_raw into an existing image with a given scale (ema.ema_update_)."""
+    L = _ffi.lib()
+    n = len(src_channels)
+    ch = (ctypes.c_int * n)(*src_channels)
+    wc = w.float().contiguous()
+    rc = L.dkt_conv_c8_pack_weights(wc.data_ptr(), ch, n, int(w.shape[0]), 1.0 / inv_scale, img.data_ptr(),
+                                    _ffi.device_of(w), _ffi.stream_of(w))
+    _ffi.check(rc, "dkt_conv_c8_pack_weights")
+
+
+def _dropper(cache, slot, p):
+    def drop():
+        lst = [q for q in cache.get(slot, ()) if q is not p]
+        if lst:
+            cache[slot] = lst
+        else:
+            cache.pop(slot, None)
+    return drop
+
+
+def _refresh_packed_c8(layer, cache, R):
+    """ema.ema_update_: the current step images of `layer` rewritten in place with their scales (see packed_weights)."""
+    for slot, lst in list(cache.items()):
+        for p in list(lst):
+            if not R.current(p.key):
+                continue
+            w, b = layer.weight, layer.bias
+            src_channels, scales = p.key[3], p.key[4]
+            wc = w.detach().float()
+            amax = R.amax(w)
+            if scales is not None:
+                wc = wc * _in_scale_vector(scales, w.device).view(1, -1, 1, 1)
+                amax = wc.abs().amax()
+            R.window(amax, p.inv_scale, _dropper(cache, slot, p))
+            _repack_raw(wc, src_channels, p.inv_scale, p.img)
+            if p.bias is not None:
+                _copy_unaliased(p.bias, b)
+            p.key = R.rekey(p.key)
+
+
+def _refresh_gru_c8(gru, cache, R):
+    """ema.ema_update_: the z|r and q images of one ConvGRU rewritten in place with their scales (see gru_packed)."""
+    for slot, lst in list(cache.items()):
+        for p in list(lst):
+            if not R.current(p.key):
+                continue
+            x_channels, hs, xs = p.key[6:9]
+            wzr, wq2, ch = _gru_images(gru, x_channels, hs, xs)
+            drop = _dropper(cache, slot, p)
+            R.window(wzr.abs().amax(), p.inv_zr, drop)
+            R.window(wq2.abs().amax(), p.inv_q, drop)
+            _repack_raw(wzr, [ch] + list(x_channels), p.inv_zr, p.wzr)
+            _repack_raw(wq2, list(x_channels) + [ch], p.inv_q, p.wq)
+            for dst, src in zip((p.bz, p.br, p.bq), (gru.convz.bias, gru.convr.bias, gru.convq.bias)):
+                _copy_unaliased(dst, src)
+            p.key = R.rekey(p.key)
+
+
+def _refresh_head_w(layer2, cache, R):
+    """ema.ema_update_: the head's second-layer weights (see _head_weights) rewritten in place."""
+    for dev, (key, t) in list(cache.items()):
+        if R.current(key):
+            w = layer2.weight
+            t[:, :, :9].copy_(w.detach().float().reshape(w.shape[0], w.shape[1], 9))
+            cache[dev] = (R.rekey(key), t)
 
 
 def gru_flags(B, H, W, device):

@@ -274,6 +274,17 @@ def _kmajor_weight(layer):
     return hit[1]
 
 
+def _refresh_kmajor(layer, cache, R):
+    """ema.ema_update_: the k-major copy of a 1x1 layer's weight (_kmajor_weight; geometry's lookup keeps the same one)
+    rewritten in place."""
+    for dev, (key, wm) in list(cache.items()):
+        if R.current(key):
+            w = layer.weight
+            from .conv import _copy_unaliased
+            _copy_unaliased(wm, w.detach().reshape(w.shape[0], -1).t())
+            cache[dev] = (R.rekey(key), wm)
+
+
 class CorrBlockFast1D(CorrBlock1D):
     """core/corr.py:31-61 ("reg_cuda").  The reference needs the un-vendored
     ``corr_sampler`` CUDA extension for this class; here it is the same HIP

@@ -1,0 +1,246 @@
+"""The EMA teacher's update of tools/ft_dkt.py:179-181, keeping the teacher's derived weights and captured loop warm.
+
+The reference rewrites every parameter of ``model_T_EMA`` before each step::
+
+    for t_params, s_params in zip(model_T_EMA.parameters(), model.parameters()):
+        t_params.data = (ema_decay * t_params.data + (1 - ema_decay) * s_params.data)
+        t_params.requires_grad = False
+
+Every weight derivative of this library (packed images, folded / merged layers, the captured loop's key) is keyed on
+``(data_ptr, _version)``, so each EMA-teacher forward after that loop is a cold start.  ``ema_update_(teacher, student,
+decay)`` computes the same values in place (``dkt_ema_update``, one launch for all parameters), bumps every parameter's
+version counter, and then rewrites every cache entry that was current before the update into its existing buffers with
+its existing scales and re-keys it.  Whatever is not rewritten -- a cache this module does not know, an entry whose
+weights left their scale window -- keeps its old key and is rebuilt cold on next use: never stale.
+
+Window: a cold pack scales max|w| into [2^12, 2^13).  A refreshed pack keeps its scale while the new max|w|
+times that scale lies in [2^11, 2^14): the hi part stays finite (2^14 is far below fp16's 65504) and the residual keeps
+at least all but one of the bits a cold pack gives it.  The check runs on the device; the flags of all packs are read with
+one host synchronisation per call.
+"""
+
+import torch
+import torch.nn as nn
+
+from . import _ffi
+from . import conv as _conv
+from . import conv_c8 as _conv_c8
+from . import corr as _corr
+from . import extractor as _extractor
+from . import update as _update
+
+#: scaled max|w| window of a refreshed pack: [2^WINDOW_LO, 2^WINDOW_HI)
+WINDOW_LO, WINDOW_HI = 11, 14
+
+
+def _zr(module, cache, R):
+    return module._refresh_zr(cache, R)
+
+
+#: derived-weight caches: refreshed first; each returns the derived layers, whose own pack caches are refreshed next
+DERIVED_HOOKS = {
+    "_dkt_folded": _extractor._refresh_folded,
+    "_dkt_merged": _extractor._refresh_merged,
+    "_zr_cache": _zr,
+    "_dkt_view": lambda layer, view, R: [v for v in [_update._refresh_view(layer, view, R)] if v is not None],
+    "_dkt_scaled": lambda layer, view, R: [v for v in [_update._refresh_view(layer, view, R)] if v is not None],
+    "_dkt_wt": lambda layer, cache, R: _corr._refresh_kmajor(layer, cache, R) or [],
+    "_dkt_head_w": lambda layer, cache, R: _conv_c8._refresh_head_w(layer, cache, R) or [],
+}
+#: packed images (split-fp16, C8S, ConvGRU, 7x7 stem): rewritten with the pack kernels at their cached scales
+PACK_HOOKS = {
+    "_dkt_packed": _conv._refresh_packed,
+    "_dkt_stem7": _conv._refresh_stem7,
+    "_dkt_packed_c8": _conv_c8._refresh_packed_c8,
+    "_dkt_gru_c8": _conv_c8._refresh_gru_c8,
+}
+#: per-layer caches that hold no weight derivative
+NOT_WEIGHTS = {"_dkt_c8_buf"}
+
+
+class _Refresh:
+    """State of one ema_update_ call: old -> new version of every tensor written, the window flags of the repacked images."""
+
+    def __init__(self):
+        self.vmap = {}            # data_ptr -> (version before, version after)
+        self.gone = set()         # data_ptrs of parameters the fallback replaced
+        self.flags, self.drops = [], []
+        self.unknown = []         # caches no hook refreshed
+        self.absmax = None
+        self.index = {}           # data_ptr -> (position in absmax, numel) of the kernel's parameters
+        self.repacked = 0
+
+    def _pairs(self, key):
+        if isinstance(key, tuple):
+            for i, x in enumerate(key):
+                if type(x) is int and i + 1 < len(key) and type(key[i + 1]) is int and (x in self.vmap or x in self.gone):
+                    yield i, x, key[i + 1]
+                elif isinstance(x, tuple):
+                    yield from self._pairs(x)
+
+    def current(self, key):
+        """True when `key` names at least one written tensor and every one at the version it had before this update."""
+        seen = False
+        for _, ptr, ver in self._pairs(key):
+            if ptr in self.gone or self.vmap[ptr][0] != ver:
+                return False
+            seen = True
+        return seen
+
+    def rekey(self, key):
+        if not isinstance(key, tuple):
+            return key
+        out = list(key)
+        for i, x in enumerate(key):
+            if type(x) is int and i + 1 < len(key) and type(key[i + 1]) is int and x in self.vmap and self.vmap[x][0] == key[i + 1]:
+                out[i + 1] = self.vmap[x][1]
+            elif isinstance(x, tuple):
+                out[i] = self.rekey(x)
+        return tuple(out)
+
+    def write(self, t, fn):
+        old = t._version
+        fn()
+        self.vmap[t.data_ptr()] = (old, t._version)
+
+    def amax(self, w):
+        """max|w| on the device: the kernel's own output when `w` is one of the updated parameters, else a reduction."""
+        hit = self.index.get(w.data_ptr())
+        if hit is not None and hit[1] == w.numel() and w.dtype == torch.float32:
+            return self.absmax[hit[0]]
+        return w.detach().float().abs().amax()
+
+    def window(self, amax, inv_scale, drop):
+        s = amax / inv_scale
+        self.flags.append((s >= 2.0 ** WINDOW_LO) & (s < 2.0 ** WINDOW_HI))
+        self.drops.append(drop)
+        self.repacked += 1
+
+
+_TABLES = {}
+
+
+def _tables(dev, ts, ss):
+    """Device tables of dkt_ema_update for this list of parameters (cached: built once per parameter set)."""
+    key = (dev, tuple(t.data_ptr() for t in ts), tuple(s.data_ptr() for s in ss), tuple(t.numel() for t in ts))
+    hit = _TABLES.get(key)
+    if hit is None:
+        off = [0]
+        for t in ts:
+            off.append(off[-1] + t.numel())
+        hit = (torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64).to(dev),
+               torch.tensor([s.data_ptr() for s in ss], dtype=torch.int64).to(dev),
+               torch.tensor(off, dtype=torch.int64).to(dev))
+        if len(_TABLES) >= 16:
+            _TABLES.pop(next(iter(_TABLES)))
+        _TABLES[key] = hit
+    return hit
+
+
+def ema_kernel(ts, ss, decay, absmax=None):
+    """t <- decay * t + (1 - decay) * s for lists of same-device, dense fp32 CUDA tensors, one launch (dkt_ema_update).
+    `absmax`: optional (len(ts),) fp32 tensor receiving max|t_new| per tensor."""
+    if not ts:
+        return
+    dev = ts[0].device
+    tp, sp, off = _tables(dev, ts, ss)
+    rc = _ffi.lib().dkt_ema_update(tp.data_ptr(), sp.data_ptr(), off.data_ptr(), len(ts), float(decay), float(1 - decay),
+                                   None if absmax is None else absmax.data_ptr(), _ffi.device_of(ts[0]), _ffi.stream_of(ts[0]))
+    _ffi.check(rc, "dkt_ema_update")
+
+
+def _kernel_ok(t, s):
+    return (t.is_cuda and s.is_cuda and t.device == s.device and t.dtype == torch.float32 and s.dtype == torch.float32
+            and t.shape == s.shape and t.is_contiguous() and s.is_contiguous())
+
+
+def _unwrap(m):
+    return m.module if isinstance(m, (nn.DataParallel, nn.parallel.DistributedDataParallel)) else m
+
+
+def _refresh(teacher, R):
+    """Rewrites every current weight derivative below `teacher` in place; returns True when the captured states may be
+    re-keyed (nothing unknown, every scale window held -- read with the call's one host synchronisation).  Derived layers
+    carry caches of their own (a folded layer's merged heads, a layer view's head weights, every pack): they are visited
+    after the layers they derive from, breadth first."""
+    todo, seen, holders = list(teacher.modules()), set(), []
+    while todo:
+        h = todo.pop(0)
+        if id(h) in seen:
+            continue
+        seen.add(id(h))
+        holders.append(h)
+        for name, val in list(h.__dict__.items()):
+            if not (name.startswith("_dkt_") or name == "_zr_cache") or val is None or (isinstance(val, dict) and not val):
+                continue
+            hook = DERIVED_HOOKS.get(name)
+            if hook is not None:
+                todo.extend(hook(h, val, R))
+            elif name not in PACK_HOOKS and name not in NOT_WEIGHTS:
+                R.unknown.append((h, name))
+    for h in holders:
+        for name, hook in PACK_HOOKS.items():
+            cache = h.__dict__.get(name)
+            if cache:
+                hook(h, cache, R)
+    ok = not R.unknown
+    if R.flags:
+        bits = torch.stack(R.flags).cpu().tolist()          # the one host read of the call
+        for good, drop in zip(bits, R.drops):
+            if not good:
+                drop()
+                ok = False
+    return ok
+
+
+def ema_update_(teacher, student, decay):
+    """In place: for every (t, s) of zip(teacher.parameters(), student.parameters()), t = decay * t + (1 - decay) * s, with
+    the result bit-identical to the reference's expression, then the teacher's weight derivatives and captured loop are
+    refreshed so that its next forward stays warm.  `teacher` / `student`: modules or nn.DataParallel wrappers.  Parameters
+    the kernel cannot take (CPU, not fp32, mismatched shapes or devices) are updated by the reference's own expression;
+    their derivatives go cold.  Returns a dict of counts (parameters by kernel / by fallback, repacked images, whether the
+    captured states were kept)."""
+    tm, sm = _unwrap(teacher), _unwrap(student)
+    decay = float(decay)
+    R = _Refresh()
+    by_dev, fallback = {}, []
+    with torch.no_grad():
+        for t, s in zip(tm.parameters(), sm.parameters()):
+            if _kernel_ok(t, s):
+                by_dev.setdefault(t.device, ([], []))
+                by_dev[t.device][0].append(t)
+                by_dev[t.device][1].append(s)
+            else:
+                fallback.append((t, s))
+        for t, s in fallback:
+            R.gone.add(t.data_ptr())
+            t.data = (decay * t.data + (1 - decay) * s.data)
+            t.requires_grad = False
+        kernel = [t for ts, _ in by_dev.values() for t in ts]
+        for dev, (ts, ss) in by_dev.items():
+            absmax = torch.empty(len(ts), device=dev, dtype=torch.float32)
+            ema_kernel(ts, ss, decay, absmax)
+            if len(by_dev) == 1:                           # (amax by reduction when the parameters span devices)
+                R.absmax = absmax
+                R.index = {t.data_ptr(): (i, t.numel()) for i, t in enumerate(ts)}
+        olds = [t._version for t in kernel]
+        if kernel:
+            torch.autograd.graph.increment_version(kernel)
+        for t, old in zip(kernel, olds):
+            R.vmap[t.data_ptr()] = (old, t._version)
+            t.requires_grad = False
+        ok = _refresh(tm, R) if kernel else False
+        if ok:
+            for m in tm.modules():
+                rekey = getattr(m, "_ema_rekey", None)
+                if rekey is not None:
+                    rekey(R)
+    return dict(kernel=len(kernel), fallback=len(fallback), repacked=R.repacked, warm=ok,
+                unknown=[name for _, name in R.unknown])
+
+
+def reference_update_(teacher, student, decay):
+    """tools/ft_dkt.py:179-181 verbatim (the fallback and the yardstick of the tests and tools/bench_ema_teacher.py)."""
+    for t_params, s_params in zip(_unwrap(teacher).parameters(), _unwrap(student).parameters()):
+        t_params.data = (decay * t_params.data + (1 - decay) * s_params.data)
+        t_params.requires_grad = False

@@ -8,6 +8,8 @@ library's kernels (1x1 / 3x3 with stride 1 or 2: dkt_conv2d_f16s[_strided]; the 
 dkt_conv2d_stem7), eval-mode BatchNorm is folded into the convolution, instance norm and the
 residual join are streaming kernels; anything else (training, CPU, group norm) is plain torch.
 """
+import weakref
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -68,6 +70,47 @@ def _tensor_key(t):
     return None if t is None else (t.data_ptr(), t._version)
 
 
+def _fold(conv, bn):
+    with torch.no_grad():
+        g = torch.rsqrt(bn.running_var.double() + bn.eps)
+        if bn.weight is not None:
+            g = g * bn.weight.double()
+        b = conv.bias.double() if conv.bias is not None else torch.zeros_like(g)
+        b = (b - bn.running_mean.double()) * g
+        if bn.bias is not None:
+            b = b + bn.bias.double()
+        return (conv.weight.double() * g.view(-1, 1, 1, 1)).float().contiguous(), b.float().contiguous()
+
+
+def _refresh_folded(conv, cache, R):
+    """ema.ema_update_: the folded weights and bias rewritten in place (same fold, same buffers); returns the folded layers."""
+    out = []
+    for slot, f in list(cache.items()):
+        bn = f.bn()
+        if bn is not None and R.current(f.key):
+            w, b = _fold(conv, bn)
+            R.write(f.weight, lambda: f.weight.copy_(w))
+            R.write(f.bias, lambda: f.bias.copy_(b))
+            f.key = R.rekey(f.key)
+            out.append(f)
+    return out
+
+
+def _refresh_merged(layer, cache, R):
+    """ema.ema_update_: the side-by-side heads (_merged_outputs) rewritten in place; returns the merged layers."""
+    out = []
+    for slot, m in list(cache.items()):
+        layers = [r() for r in m.layers]
+        if all(l is not None for l in layers) and R.current(m.key):
+            R.write(m.weight, lambda: torch.cat([l.weight.detach().float() for l in layers], 0, out=m.weight))
+            R.write(m.bias, lambda: torch.cat([(l.bias.detach().float() if l.bias is not None else
+                                                torch.zeros(l.weight.shape[0], device=l.weight.device)) for l in layers], 0,
+                                               out=m.bias))
+            m.key = R.rekey(m.key)
+            out.append(m)
+    return out
+
+
 def _folded(conv, bn):
     """conv followed by bn (running statistics):  bn(conv(x)) = conv'(x) with
     w' = w * g, b' = (b - mean) * g + beta, g = gamma / sqrt(var + eps)  (per output channel).
@@ -83,22 +126,14 @@ def _folded_locked(conv, bn):
     hit = cache.get(slot)
     if hit is not None and hit.key == key:
         return hit
-    with torch.no_grad():
-        g = torch.rsqrt(bn.running_var.double() + bn.eps)
-        if bn.weight is not None:
-            g = g * bn.weight.double()
-        b = conv.bias.double() if conv.bias is not None else torch.zeros_like(g)
-        b = (b - bn.running_mean.double()) * g
-        if bn.bias is not None:
-            b = b + bn.bias.double()
-        f = _Folded()
-        f.weight = (conv.weight.double() * g.view(-1, 1, 1, 1)).float().contiguous()
-        f.bias = b.float().contiguous()
+    f = _Folded()
+    f.weight, f.bias = _fold(conv, bn)
     f.padding = conv.padding
     f.stride = conv.stride
     f.dilation = conv.dilation        # conv2d sends dilated / grouped layers to the vendor library
     f.groups = conv.groups
     f.key = key
+    f.bn = weakref.ref(bn)            # (for ema.ema_update_; weak: the cache must not tie the modules into a cycle)
     cache[slot] = f
     return f
 
@@ -336,6 +371,7 @@ def _merged_outputs(layers):
                                  torch.zeros(l.weight.shape[0], device=l.weight.device)) for l in layers], 0).contiguous()
         m.padding, m.stride, m.dilation, m.groups = layers[0].padding, layers[0].stride, layers[0].dilation, layers[0].groups
         m.key = key
+        m.layers = [weakref.ref(l) for l in layers]      # (for ema.ema_update_; weak: no cycle through layers[0]'s cache)
         cache[slot] = m
         return m
 

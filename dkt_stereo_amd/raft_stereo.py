@@ -550,6 +550,20 @@ class RAFTStereo(nn.Module):
                 fp.append(("in_exp", id(m), e))
         return tuple(fp)
 
+    def _ema_rekey(self, R):
+        """ema.ema_update_ has rewritten every weight derivative of this model in place: the captured loop and encoder
+        pass of every thread read the same buffers, so their keys move to the new parameter versions instead of
+        being rebuilt.  (A state already stale before the update stays stale, and so does a loop that points to a
+        packed image the refresh did not reach: one evicted from its layer's cache but still pinned by a capture.)"""
+        with _GRAPH_LOCK:
+            for states in (_GRAPH_STATES.get(self, {}), _ENCODER_STATES.get(self, {})):
+                for st in states.values():
+                    lp = st.get("c8")
+                    if lp is not None and any(R.current(getattr(p, "key", None)) for p in lp.pinned):
+                        continue
+                    if R.current(st["key"]):
+                        st["key"] = R.rekey(st["key"])
+
     def _one_iteration_pipelined(self, corr_fn, coords0, coords1, net_state, inp_list, need_mask, last):
         """raft_stereo.py:146-167 with the two coarse GRUs off the critical path.  Precondition:
         net_state[2] already holds gru32 of THIS iteration (prologue / previous call); unless

@@ -20,6 +20,7 @@ Convolutions go through ``dkt_stereo_amd.conv.conv2d`` (see that module).
 Inference only.
 """
 import contextlib
+import gc
 import os
 import threading
 from types import SimpleNamespace
@@ -112,9 +113,17 @@ GPU_GUARD = _CaptureGuard()
 
 @contextlib.contextmanager
 def capture_graph(graph):
-    with GPU_GUARD.exclusive():
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            yield
+    # no cyclic garbage collection while capturing: a collected CUDAGraph (an earlier captured state that became cyclic
+    # garbage) would be destroyed inside the capture, which the runtime refuses with an abort
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with GPU_GUARD.exclusive():
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 def replay_graph(graph):
@@ -230,6 +239,20 @@ def _leading_outputs(layer, n):
     return view
 
 
+def _refresh_view(layer, view, R):
+    """ema.ema_update_: a _LayerView's tensors are views of the layer's own (already updated): only its key moves.  A
+    _ScaledLayer's copies are rewritten in place.  Returns the view (its own caches are refreshed next)."""
+    if not R.current(view._key):
+        return None
+    if isinstance(view, _ScaledLayer):
+        scale = view._key[3][1]
+        R.write(view.weight, lambda: torch.mul(layer.weight.detach(), scale, out=view.weight))
+        if view.bias is not None:
+            R.write(view.bias, lambda: torch.mul(layer.bias.detach(), scale, out=view.bias))
+    view._key = R.rekey(view._key)
+    return view
+
+
 class DispHead(FlowHead):
     """meta_arch/igev_stereo/update.py:16-24."""
 
@@ -271,9 +294,8 @@ class ConvGRU(nn.Module):
         """convz | convr as one Conv2d-like (weight, bias) pair per device, rebuilt whenever
         either parameter tensor is replaced or written (load_state_dict, .to())."""
         wz, wr = self.convz.weight, self.convr.weight
-        key = (wz.data_ptr(), wr.data_ptr(), wz._version, wr._version,
-               self.convz.bias.data_ptr(), self.convr.bias.data_ptr(),
-               self.convz.bias._version, self.convr.bias._version)
+        bz, br = self.convz.bias, self.convr.bias
+        key = tuple((t.data_ptr(), t._version) for t in (wz, wr, bz, br))
         with _CACHE_LOCK:
             cache = self._zr_cache
             if cache is None:
@@ -285,6 +307,17 @@ class ConvGRU(nn.Module):
                                    torch.cat([self.convz.bias, self.convr.bias], dim=0).contiguous())
                 hit = cache[str(wz.device)] = (key, zr)
             return hit[1]
+
+    def _refresh_zr(self, cache, R):
+        """ema.ema_update_: the merged z|r layer rewritten in place; returns the merged layers (their caches come next)."""
+        out = []
+        for dev, (key, zr) in list(cache.items()):
+            if R.current(key):
+                R.write(zr.weight, lambda: torch.cat([self.convz.weight.detach(), self.convr.weight.detach()], dim=0, out=zr.weight))
+                R.write(zr.bias, lambda: torch.cat([self.convz.bias.detach(), self.convr.bias.detach()], dim=0, out=zr.bias))
+                cache[dev] = (R.rekey(key), zr)
+                out.append(zr)
+        return out
 
     def forward(self, h, cz, cr, cq, *x_list, out=None):
         """`out` (optional, may be `h`): where the new hidden state is written."""

@@ -441,6 +441,18 @@ int dkt_instance_norm_finalize(const void *workspace, int planes, long HW, float
 
 int dkt_add_relu(const float *a, const float *b, float *y, long n, int device, void *stream);
 
+/* ---- EMA teacher update (csrc/ema.hip) ----------------------------------------------------------------------
+ * Replaces the loop of tools/ft_dkt.py:179-181,
+ *     t_params.data = (ema_decay * t_params.data + (1 - ema_decay) * s_params.data)
+ * for `count` tensors in ONE launch: t[i][j] = fl(fl(decay * t[i][j]) + fl(one_minus_decay * s[i][j])), two fp32
+ * roundings, bit-identical to torch's evaluation of the expression (Python forms 1 - ema_decay in double; torch rounds
+ * both scalars to fp32).  t, s: DEVICE tables of `count` tensor pointers (fp32, dense); n: DEVICE table of count + 1
+ * exclusive prefix offsets (n[0] = 0, n[i+1] - n[i] = numel of tensor i, may be 0).  absmax (may be null): `count`
+ * floats, max |t_new| per tensor (0 for an empty tensor), deterministic.  count = 0 is a no-op.  Errors: count < 0
+ * DKT_E_SHAPE, a table null DKT_E_NULL, a non-finite decay DKT_E_UNSUPPORTED. */
+int dkt_ema_update(float *const *t, const float *const *s, const long *n, int count, float decay, float one_minus_decay,
+                   float *absmax, int device, void *stream);
+
 /* ---- round 3: the 3x3 convolution on pre-split activations ("C8S" layout, conv_c8.hip) -------------------------
  * Same operator and arithmetic as dkt_conv2d_f16s(passes = 3) -- core/update.py:19-21,27-31 (ConvGRU), :72-76,84
  * (motion encoder), :9 (FlowHead.conv1) -- but the activation operands arrive as fp16 (hi, lo) pairs written by the
