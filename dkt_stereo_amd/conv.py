@@ -491,8 +491,8 @@ def stats_eligible(layer):
     return hip_eligible(layer) and _stride_of(layer) in ((1, 1), (2, 2)) and not direct_eligible(layer) and not few_eligible(layer)
 
 
-def conv2d_stats(x, layer, in_norm=None, _ws=None):
-    """conv(x) + bias with the statistics of its OWN output for the InstanceNorm2d that follows it
+def conv2d_stats(x, layer, in_norm=None, _ws=None, relu=False):
+    """conv(x) + bias [ReLU] with the statistics of its OWN output for the InstanceNorm2d that follows it
     (core/extractor.py:46-50): returns (out, OutStats).  `in_norm` as in conv2d_fused (stride 1 only).
     `_ws`: the per-(tile, wave row) scratch of dkt_conv2d_stats_ws_floats floats, handed in by the guarded-buffer test."""
     op = _Operands(x, layer)
@@ -500,7 +500,7 @@ def conv2d_stats(x, layer, in_norm=None, _ws=None):
     Ho, Wo = (op.H - 1) // stride + 1, (op.W - 1) // stride + 1
     out = torch.empty((op.B, op.cout, Ho, Wo), device=op.device, dtype=torch.float32)
     L = _ffi.lib()
-    d = _desc(op, out)
+    d = _desc(op, out, relu=relu)
     d.stride = stride
     planes = op.B * op.cout
     n_ws = int(L.dkt_conv2d_stats_ws_floats(op.B, op.cout, Ho, Wo))

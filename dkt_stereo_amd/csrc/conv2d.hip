@@ -107,7 +107,9 @@ struct ConvArgs {
     int src_px, src_w;
     long src_hw;
 };
-int conv_stats_reduce(const float *ws, double *part, int B, int C, long entries, long HW, hipStream_t st);      // norm.hip
+// norm.hip: folds stats_ws into stats_part, then recomputes from `out` the planes whose fp32 sums are ill-conditioned
+int conv_stats_reduce(const float *ws, double *part, int B, int C, long entries, long HW, const float *out, long out_bs,
+                      hipStream_t st);
 
 // Gate non-linearities for the fused epilogues.  The epilogue runs on the VALU after the
 // MFMA loop with nothing to overlap it, so it uses the hardware transcendentals
@@ -704,7 +706,7 @@ static int launch_conv(ConvArgs a, int B, hipStream_t st, const ConvSecond *sec 
         hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(64 * WM * WN), lds, st, ap, (int)nblk);
         int rc = dkt_launch_status();
         if (rc == DKT_OK && a.stats_ws)
-            rc = conv_stats_reduce(a.stats_ws, a.stats_part, B, a.Cout, (long)a.tiles_xy * WN, (long)a.Ho * a.Wo, st);
+            rc = conv_stats_reduce(a.stats_ws, a.stats_part, B, a.Cout, (long)a.tiles_xy * WN, (long)a.Ho * a.Wo, a.out, a.out_bs, st);
         return rc;
     }
     if (a.stats_ws || sec->a.stats_ws) return DKT_E_UNSUPPORTED;

@@ -500,6 +500,6 @@ static int launch_conv_ws(ConvArgs a, int B, hipStream_t st) {
     (void)hipLaunchKernel(kern, dim3((unsigned)nblk), dim3(256), params, lds, st);
     int rc = dkt_launch_status();
     if (rc == DKT_OK && a.stats_ws)
-        rc = conv_stats_reduce(a.stats_ws, a.stats_part, B, a.Cout, (long)a.tiles_xy * 2, (long)a.H * a.W, st);
+        rc = conv_stats_reduce(a.stats_ws, a.stats_part, B, a.Cout, (long)a.tiles_xy * 2, (long)a.H * a.W, a.out, a.out_bs, st);
     return rc;
 }

@@ -100,45 +100,77 @@ static int instnorm_split(int planes, long HW) {
     return S;
 }
 
-// Statistics accumulated by a convolution's epilogue (conv2d.hip, ConvArgs.stats_ws: per (batch, entry, channel) fp32 sums
-// and sums of squares) folded into the partial-sum workspace the kernels above read: part[(plane * S + s) * 2 + {0, 1}].
-__global__ __launch_bounds__(256) void conv_stats_reduce_kernel(const float *__restrict__ ws, double *__restrict__ part,
-                                                                int C, long E, int S) {
-    const int plane = blockIdx.y, s = blockIdx.x;
-    const int b = plane / C, c = plane - b * C;
-    const long per = (E + S - 1) / S;
-    const long lo = (long)s * per;
-    long hi = lo + per;
-    if (hi > E) hi = E;
-    double sum = 0.0, sq = 0.0;
-    for (long e = lo + threadIdx.x; e < hi; e += 256) {
-        const float2 v = *(const float2 *)(ws + (((long)b * E + e) * C + c) * 2);
-        sum += (double)v.x;
-        sq += (double)v.y;
-    }
+// (sum, sum of squares) of one block, in fp64, returned to every thread; `red` is reused across calls
+__device__ __forceinline__ void block_sum2(double &sum, double &sq, double (*red)[4]) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         sum += __shfl_down(sum, o);
         sq += __shfl_down(sq, o);
     }
-    __shared__ double red[2][4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();                     // (a previous call's readers are done with `red`)
     if (lane == 0) {
         red[0][w] = sum;
         red[1][w] = sq;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        part[((long)plane * S + s) * 2] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        part[((long)plane * S + s) * 2 + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    sum = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    sq = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+}
+
+// Statistics accumulated by a convolution's epilogue (conv2d.hip, ConvArgs.stats_ws: per (batch, entry, channel) fp32 sums
+// and sums of squares) folded into the partial-sum workspace the kernels above read, part[(plane * S + s) * 2 + {0, 1}]:
+// one block per plane writes the plane's fp64 totals to partial 0 and zeroes the other S - 1.
+// The epilogue's sums are fp32, and E[x^2] - mean^2 cancels when a plane's mean is much larger than its spread: 1/std is off
+// by ~5e-7 at mean / sigma = 10, 3e-5 at 100, 2e-3 at 1000, and the variance of a small plane at 10^4 goes negative.  A plane
+// with mean^2 > CONV_STATS_TRUST * var (or a negative / NaN variance) is therefore recomputed by the same block from the
+// stored output with fp64 squares, the arithmetic of instnorm_stats_kernel: a full read of that plane, only for such planes.
+#define CONV_STATS_TRUST 16.0
+__global__ __launch_bounds__(256) void conv_stats_reduce_kernel(const float *__restrict__ ws, double *__restrict__ part,
+                                                                int C, long E, int S, const float *__restrict__ out,
+                                                                long out_bs, long HW) {
+    const int plane = blockIdx.x;
+    const int b = plane / C, c = plane - b * C;
+    __shared__ double red[2][4];
+    double sum = 0.0, sq = 0.0;
+    for (long e = threadIdx.x; e < E; e += 256) {
+        const float2 v = *(const float2 *)(ws + (((long)b * E + e) * C + c) * 2);
+        sum += (double)v.x;
+        sq += (double)v.y;
+    }
+    block_sum2(sum, sq, red);
+    const double mean = sum / (double)HW, var = sq / (double)HW - mean * mean;
+    if (!(mean * mean <= CONV_STATS_TRUST * var)) {         // block-uniform (also true for a NaN or a negative variance)
+        const float *p = out + (long)b * out_bs + (long)c * HW;
+        sum = sq = 0.0;
+        if (((uintptr_t)p & 15) == 0 && (HW & 3) == 0) {
+            for (long i = 4L * threadIdx.x; i < HW; i += 1024) {
+                const float4 v = *(const float4 *)(p + i);
+                sum += (double)v.x + (double)v.y + (double)v.z + (double)v.w;
+                sq += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+            }
+        } else {
+            for (long i = threadIdx.x; i < HW; i += 256) {
+                const double v = p[i];
+                sum += v;
+                sq += v * v;
+            }
+        }
+        block_sum2(sum, sq, red);
+    }
+    for (int s = threadIdx.x; s < S; s += 256) {
+        part[((long)plane * S + s) * 2] = s ? 0.0 : sum;
+        part[((long)plane * S + s) * 2 + 1] = s ? 0.0 : sq;
     }
 }
 
-int conv_stats_reduce(const float *ws, double *part, int B, int C, long entries, long HW, hipStream_t st) {
+int conv_stats_reduce(const float *ws, double *part, int B, int C, long entries, long HW, const float *out, long out_bs,
+                      hipStream_t st) {
     const long planes = (long)B * C;
     if (planes <= 0 || planes > 65535 || entries <= 0) return DKT_E_SHAPE;
     const int S = instnorm_split((int)planes, HW);
-    hipLaunchKernelGGL(conv_stats_reduce_kernel, dim3((unsigned)S, (unsigned)planes), dim3(256), 0, st, ws, part, C, entries, S);
+    hipLaunchKernelGGL(conv_stats_reduce_kernel, dim3((unsigned)planes), dim3(256), 0, st, ws, part, C, entries, S, out,
+                       out_bs, HW);
     return dkt_launch_status();
 }
 
