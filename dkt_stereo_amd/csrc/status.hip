@@ -3,7 +3,7 @@
 // RAFTStereo.forward / igev_iterate verify three things behind every pair (raft_stereo.py:85-187 has no such check: the
 // reference computes in fp32 and has no flag protocol -- these are the conditions under which THIS implementation equals it):
 //   * the result is finite (split-fp16 convolutions turn an out-of-range activation into Inf / NaN instead of saturating),
-//   * no fused ConvGRU / chain launch gave up waiting for a neighbour tile (gru_c8.hip: the error word),
+//   * no fused ConvGRU launch gave up waiting for a neighbour tile (gru_c8.hip: bit 0 of the error word, its only bit),
 //   * the C8S tensors whose magnitude follows the input still sit inside the window their scales were picked for.
 // Round 5 did that with three host synchronisations and ~10 torch reductions per forward; this kernel folds all of it into
 // one pass: maxima as fp16 bit patterns of |hi| (monotone for non-negative values; a NaN pattern is larger than Inf's, so

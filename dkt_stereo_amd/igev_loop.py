@@ -15,7 +15,6 @@ library.
 """
 import os
 import threading
-import warnings
 import weakref
 
 import torch
@@ -371,14 +370,9 @@ def _igev_iterate(update_block, geo_fn, init_disp, coords, net_list, inp_list, i
             raise _conv._ffi.DktError("igev_iterate produced a non-finite disparity: an activation left the range of the "
                                       "split-fp16 convolutions (or the inputs were not finite)")
         if word:
-            # a fused ConvGRU (bit 0) or chain (bit 1) launch gave up waiting for a neighbour tile (csrc/gru_c8.hip; ADVICE
-            # r04): the result is wrong.  That form is left for good, and this call is computed again from the caller's
-            # (untouched) inputs.
-            if getattr(st.c8, "timed_out", 0) & word:
-                raise _conv._ffi.DktError("the IGEV loop reported a flag time-out in a form that had already been switched off")
-            st.c8.timed_out = getattr(st.c8, "timed_out", 0) | word
-            warnings.warn("dkt_stereo_amd: a %s launch timed out waiting for a neighbour tile; falling back to separate "
-                          "launches for this update block (one fused-GRU model per device)" % ("fused ConvGRU" if word & 1 else "chain"))
+            # a fused ConvGRU launch gave up waiting for a neighbour tile (csrc/gru_c8.hip): the result is wrong.
+            # The loop falls back to the two-launch form (or raises, if it already had), and this call is computed again from
+            # the caller's (untouched) inputs.
             st.c8.on_error_word(word)
             return _igev_iterate(update_block, geo_fn, init_disp, coords, net_list, inp_list, iters, use_hip_graph,
                                  cache if cache is not None else dict(state=st))

@@ -10,6 +10,7 @@ overlap usefully on this part, tools/concurrency_probe.py):
 Every GRU sees exactly the operands of the reference's sequential order."""
 import math
 import os
+import warnings
 
 import torch
 
@@ -67,7 +68,6 @@ SCALE_EXP = 10
 RANGE_LO, RANGE_HI = 6, 14
 
 #: the middle GRU's chain of the next iteration on a second stream beside the head and the motion encoder (DKT_C8_FORK=0: one stream)
-#: (=2: also the motion encoder's 7x7 stem beside the lookup on a third stream -- measured 0.25 ms per pair SLOWER, kept for A/B)
 FORK = int(os.environ.get("DKT_C8_FORK", "1"))
 #: the prologue's motion features beside its hidden-state chain (see C8Loop.prologue)
 PROLOGUE_FORK = True
@@ -78,13 +78,6 @@ FRONT = True
 PAIR_RESAMPLE = True
 #: the flow head is the fused GRU launch's first successor in the captured unit (see C8Loop.unit)
 HEAD_FIRST = True
-#: round 5 prototype: dependent layer pairs of the window between two fused-GRU launches as ONE
-#: launch each, a flag round instead of the kernel boundary (dkt_conv2d_c8_chain): convc2 | convf2 -> encoder.conv on the main
-#: queue, the middle GRU's z|r -> q on the forked one.  0 = off (default: measured, profiles/r05_chain.txt), 1 = on,
-#: 2 = timing only (no waits: the upper bound of what the fusion can buy; results are wrong).  Both chains can be in flight at
-#: once, and every block of a chain must stay resident while it waits: CHAIN_BLOCKS each
-CHAIN = int(os.environ.get("DKT_C8_CHAIN", "0"))
-CHAIN_BLOCKS = int(os.environ.get("DKT_C8_CHAIN_BLOCKS", "256"))
 #: units per captured graph: a replay boundary costs ~8 us of idle device between two units (profiles/r04_pair_breakdown.txt), so
 #: the bulk of the iterations is replayed GRAPH_UNITS units at a time (a one-unit graph serves the remainder)
 GRAPH_UNITS = max(1, int(os.environ.get("DKT_C8_GRAPH_UNITS", "8")))
@@ -193,11 +186,7 @@ class C8Loop:
         self.graph_last = None           # [parity] the final unit of a pair
         self.pinned = []                 # packed weight images the captured units point to (see capture)
         self.unit_launches = None
-        self.chain_flags, self.chain_z = {}, {}          # dkt_conv2d_c8_chain: flag words per layer pair, z of the middle GRU
-        self.chain_ok = True
-        if CHAIN == 2:
-            import warnings
-            warnings.warn("DKT_C8_CHAIN=2: chain launches run WITHOUT their waits (a timing experiment): results are wrong")
+        self.timed_out = False           # a flag time-out has already switched the fused ConvGRU off (see on_error_word)
         self.front = bool(FRONT) and self._front_supported(st)
         mask = getattr(ub, "mask", None)               # (IGEV's mask features are computed by its caller)
         self.mask_head = mask if (mask is not None and len(mask) == 3 and isinstance(mask[0], torch.nn.Conv2d)
@@ -365,7 +354,7 @@ class C8Loop:
         return bool(self.take_error_word())
 
     def take_error_word(self):
-        """The error word itself (and clears it): bit 0 = a fused ConvGRU launch timed out, bit 1 = a chain launch did."""
+        """The error word itself (and clears it): non-zero (bit 0, the only one) = a fused ConvGRU launch timed out."""
         word = int(self.err.item())
         if word:
             self.err.zero_()
@@ -432,22 +421,22 @@ class C8Loop:
         """The two-launch form of the finest ConvGRU from here on (after a flag time-out: this device does not keep the
         launch's blocks resident, e.g. another process holds part of the CUs); captured units are dropped."""
         self.fuse_gru = False
-        self.disable_chains()            # (the chain launches wait on flags the same way)
-
-    def disable_chains(self):
-        """No chain launches from here on (a chain's own time-out -- bit 1 of the error word -- leaves the fused ConvGRU
-        launch alone: ADVICE r05); captured units are dropped."""
-        self.chain_ok = False
         self.graph = self.graph_n = self.graph_last = None
         self.pinned = []
         self.par = 0
 
     def on_error_word(self, word):
-        """Falls back from whichever flag-synchronised form raised `word` (take_error_word / status().err)."""
-        if word & 1:
-            self.disable_fused_gru()
-        elif word & 2:
-            self.disable_chains()
+        """The time-out policy of the checked forwards, for a non-zero error word (take_error_word / status().err): a fused
+        ConvGRU launch gave up waiting for a neighbour tile (csrc/gru_c8.hip: its blocks were not all resident -- another
+        process or model on this device), so the result is wrong.  The first time, a warning and the two-launch form for good
+        (the caller then computes the result again); on a loop that has already fallen back, a DktError."""
+        if self.timed_out:
+            raise _ffi.DktError("the refinement loop reported a flag time-out after its fused ConvGRU launch had been switched "
+                                "off (error word %d)" % word)
+        self.timed_out = True
+        warnings.warn("dkt_stereo_amd: a fused ConvGRU launch timed out waiting for a neighbour tile; falling back to separate "
+                      "launches for this model (one fused-GRU model per device)")
+        self.disable_fused_gru()
 
     def ranges_ok(self):
         """False when a tensor's maximum has left [2^RANGE_LO, 2^RANGE_HI) under its scale (another kind of input than the one
@@ -465,26 +454,9 @@ class C8Loop:
         return ub.gru08, ub.gru16, ub.gru32
 
     # ---- pieces -------------------------------------------------------------------------------------------------
-    def _chain_flags(self, key, d0, cfg0, nprob):
-        f = self.chain_flags.get(key)
-        if f is None:
-            f = self.chain_flags[key] = c8.chain_flags(d0, cfg0, nprob, self.err.device)
-        return f
-
-    def _gru(self, lvl, gru, st, xs, cfg_zr, cfg_q, chain=False):
+    def _gru(self, lvl, gru, st, xs, cfg_zr, cfg_q):
         h = st["net"][lvl]
         cz, cr, cq = st["inp"][lvl]
-        if chain and CHAIN and self.chain_ok and cfg_zr == 4 and cfg_q == 4:
-            # z|r + gates -> q + state update as ONE launch: a q tile waits for the z|r tiles of its 3x3 neighbourhood (all four
-            # channel blocks: they have read every patch of the old state by then, so the in-place update is safe)
-            z = self.chain_z.get(lvl)
-            if z is None:
-                z = self.chain_z[lvl] = torch.empty_like(h)
-            d0 = c8.desc([self.hc8[lvl], *xs], gru._merged_zr(), out=z, epilogue=1, e0=cz, e1=cr, h=h, out2_c8=self.rh[lvl])
-            d1 = c8.desc([self.rh[lvl], *xs], gru.convq, out=h, out_c8=self.hc8[lvl], epilogue=2, e0=cq, e1=z, h=h)
-            if c8.launch_chain(d0, None, 4, d1, 4, self._chain_flags(("gru", lvl), d0, 4, 1), h, err=self.err,
-                               max_blocks=CHAIN_BLOCKS, timing_only=(CHAIN == 2)):
-                return
         z = c8.gate_zr([self.hc8[lvl], *xs], gru._merged_zr(), cz, cr, h, rh_c8=self.rh[lvl], cfg=cfg_zr)
         c8.gate_out([self.rh[lvl], *xs], gru.convq, cq, z, h, h, out_c8=self.hc8[lvl], cfg=cfg_q)
 
@@ -518,39 +490,20 @@ class C8Loop:
             ds.append(c8.desc([self.rh[lvl], *xs], gru.convq, out=h, out_c8=self.hc8[lvl], epilogue=2, e0=cq, e1=z, h=h))
         c8.launch_pair(ds[0], ds[1], zs[0], self.cfg["q08"])
 
-    def _fork_stem(self, ref, fn):
-        """The motion encoder's 7x7 stem beside the lookup (independent until convc2 | convf2 joins them): a third stream."""
-        if FORK < 2:
-            fn()
-            return lambda: None
-        from .update import _side_stream
-        main = torch.cuda.current_stream(ref.device)
-        side = _side_stream(ref.device, slot=1)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            fn()
-        return lambda: main.wait_stream(side)
-
     def _motion_front(self, st):
         """convf1 on the flow and the lookup + convc1 (core/update.py:76-77): two launches behind the head's own finish."""
         enc = self.ub.encoder
-        join = self._fork_stem(st["flow"], lambda: c8.stem7_c8(st["flow"], enc.convf1, self.flo))
+        c8.stem7_c8(st["flow"], enc.convf1, self.flo)
         if st["corr"].lookup_conv1x1(st["coords1"], enc.convc1, out_c8=self.cor) is None:
             cor = st["corr"].lookup_conv1x1(st["coords1"], enc.convc1)
             if cor is None:       # (row-layout pyramid, other level counts / radii: the lookup tensor, then the 1x1 layer)
                 cor = _conv.conv2d(st["corr"](st["coords1"]), enc.convc1, relu=True)
             c8.pack(cor, self.cor)
-        join()
 
-    def _motion_tail(self, st, chain=False):
+    def _motion_tail(self, st):
         enc = self.ub.encoder
         d0 = c8.desc([self.cor], enc.convc2, relu=True, out_c8=self.cf, out_c8_ch0=0)
         d1 = c8.desc([self.flo], enc.convf2, relu=True, out_c8=self.cf, out_c8_ch0=64)
-        if chain and CHAIN and self.chain_ok and self.cfg["c2"] == 4 and self.cfg["enc"] == 3:
-            d2 = c8.desc([self.cf], enc.conv, relu=True, out_c8=self.mf, tail=st["flow"])
-            if c8.launch_chain(d0, d1, 4, d2, 3, self._chain_flags("enc", d0, 4, 2), st["flow"], err=self.err,
-                               max_blocks=CHAIN_BLOCKS, timing_only=(CHAIN == 2)):
-                return
         c8.launch_pair(d0, d1, st["flow"], self.cfg["c2"])
         c8.conv2d_c8([self.cf], enc.conv, relu=True, out_c8=self.mf, tail=st["flow"], cfg=self.cfg["enc"])
 
@@ -600,14 +553,14 @@ class C8Loop:
         hid = c8.conv2d_c8([self.hc8[0]], mh[0], relu=True, cfg=1)
         self.mask_out = _conv.conv2d(hid, _scaled_layer(mh[2], 0.25), out=self.mask_out)
 
-    def _mid(self, st, chain=False):
+    def _mid(self, st):
         n0, n1, n2 = st["net"]
         if PAIR_RESAMPLE:
             c8.resample_pair_c8(("pool", n0, self.pool0), ("interp", n2, self.up2))
         else:
             c8.pool2x_c8(n0, self.pool0)
             c8.interp_c8(n2, self.up2)
-        self._gru(1, self.grus[1], st, [self.pool0, self.up2], self.cfg["zr16"], self.cfg["q16"], chain=chain)
+        self._gru(1, self.grus[1], st, [self.pool0, self.up2], self.cfg["zr16"], self.cfg["q16"])
         if PAIR_RESAMPLE:
             c8.resample_pair_c8(("interp", n1, self.up1), ("pool", n1, self.pool1))
         else:
@@ -653,19 +606,19 @@ class C8Loop:
             else:
                 side.wait_stream(main)
             with torch.cuda.stream(side):
-                self._mid(st, chain=True)
+                self._mid(st)
             if not HEAD_FIRST:
                 self._head(st, front)
             if not front:
                 self._motion_front(st)
-            self._motion_tail(st, chain=True)
+            self._motion_tail(st)
             main.wait_stream(side)
         else:
             self._head(st, front)
-            self._mid(st, chain=True)
+            self._mid(st)
             if not front:
                 self._motion_front(st)
-            self._motion_tail(st, chain=True)
+            self._motion_tail(st)
 
     def prologue(self, st):
         """Per pair: hidden states into their C8S twins, the coarsest and the middle GRU of iteration 0 and its motion features."""
@@ -712,22 +665,16 @@ class C8LoopIGEV(C8Loop):
 
     def _motion_front(self, st):
         enc = self.ub.encoder
+        c8.stem7_c8(st["disp"], enc.convd1, self.flo)
         # geometry lookup + convc1 + ReLU in one kernel, straight into the C8S operand (dkt_geo_lookup_conv1x1)
-        join = self._fork_stem(st["disp"], lambda: c8.stem7_c8(st["disp"], enc.convd1, self.flo))
         if st["geo_fn"].lookup_conv1x1(st["disp"], st["coords"], enc.convc1, out_c8=self.cor) is None:
             geo = st["geo_fn"](st["disp"], st["coords"])
             c8.pack(_conv.conv2d(geo, enc.convc1, relu=True), self.cor)
-        join()
 
-    def _motion_tail(self, st, chain=False):
+    def _motion_tail(self, st):
         enc = self.ub.encoder
         d0 = c8.desc([self.cor], enc.convc2, relu=True, out_c8=self.cf, out_c8_ch0=0)
         d1 = c8.desc([self.flo], enc.convd2, relu=True, out_c8=self.cf, out_c8_ch0=64)
-        if chain and CHAIN and self.chain_ok and self.cfg["c2"] == 4 and self.cfg["enc"] == 3:
-            d2 = c8.desc([self.cf], enc.conv, relu=True, out_c8=self.mf, tail=st["disp"])
-            if c8.launch_chain(d0, d1, 4, d2, 3, self._chain_flags("enc", d0, 4, 2), st["disp"], err=self.err,
-                               max_blocks=CHAIN_BLOCKS, timing_only=(CHAIN == 2)):
-                return
         c8.launch_pair(d0, d1, st["disp"], self.cfg["c2"])
         c8.conv2d_c8([self.cf], enc.conv, relu=True, out_c8=self.mf, tail=st["disp"], cfg=self.cfg["enc"])
 

@@ -17,7 +17,6 @@ correlation block and the update operator as autograd nodes on this library's ke
 import itertools
 import math
 import os
-import warnings
 import threading
 import weakref
 from concurrent.futures import ThreadPoolExecutor
@@ -884,16 +883,8 @@ class RAFTStereo(nn.Module):
             return
         s = lp.status(flow_up)               # one launch, one host synchronisation (csrc/status.hip)
         if s.err:
-            # A fused ConvGRU (bit 0) or chain (bit 1) launch gave up waiting for a neighbour tile (csrc/gru_c8.hip: its
-            # blocks were not all resident -- another process or model on this device): this result is wrong.  The word is
-            # cleared, the loop leaves that form for good and the pair is computed again.
-            if getattr(lp, "timed_out", 0) & s.err:
-                raise _ffi.DktError("the refinement loop reported a flag time-out in a form that had already been switched off "
-                                    "(csrc/gru_c8.hip, conv_c8.hip)")
-            lp.timed_out = getattr(lp, "timed_out", 0) | s.err
-            warnings.warn("dkt_stereo_amd: a %s launch timed out waiting for a neighbour tile; falling back to separate "
-                          "launches for this model (one fused-GRU model per device)"
-                          % ("fused ConvGRU" if s.err & 1 else "chain"))
+            # A fused ConvGRU launch gave up waiting for a neighbour tile: this result is wrong.  The word is cleared, the loop
+            # falls back to the two-launch form (or raises, if it already had) and the pair is computed again.
             lp.on_error_word(s.err)
             raise _RetryForward("flag time-out")
         if lp.calibrated and not (s.finite and s.ranges_ok):

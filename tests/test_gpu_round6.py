@@ -1,8 +1,8 @@
 """-m gpu: round 6.
 
 * the post-conditions of a pair in one launch (csrc/status.hip, dkt_loop_status) against torch's reductions, and through the
-  raw ABI; the checked forward on top of it: a GRU time-out (bit 0) and a chain time-out (bit 1) fall back separately, direct
-  callers of encode() + iterate() are covered too;
+  raw ABI; the checked forward on top of it: a fused-GRU time-out falls back to separate launches once and is an error after
+  that, direct callers of encode() + iterate() are covered too;
 * args.mixed_precision (raft_stereo.py:95,156; tools/ft_dkt.py:317): False stays the parity path bit for bit, True runs the
   one-product schedule, encoders included, with its measured distance from the reference fixture;
 * IGEV's loop under nn.DataParallel replicas on a persistent per-device copy (igev_loop._ShadowBlock);
@@ -94,24 +94,23 @@ def test_loop_status_argument_errors():
 
 # ---- the checked forward ----------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def test_chain_timeout_leaves_the_fused_gru_alone():
-    """Bit 1 of the error word (a chain launch's time-out) switches the chains off, not the unrelated fused ConvGRU launch
-    (ADVICE r05); bit 0 switches both off."""
+def test_gru_timeout_falls_back_once_then_raises():
+    """A raised error word (a fused ConvGRU launch's time-out) switches the fused launch off with a warning and repeats the
+    pair; a second one on the same model, whose loop has already fallen back, is a DktError."""
+    from dkt_stereo_amd import _ffi
     H, W = 544, 960
     i1, i2 = (G(t) for t in _synth.image_pair(6, 1, H, W, 12))
     model, _ = _raft()
     _, first = model(i1, i2, iters=4, test_mode=True)
     lp = model._graph_state["c8"]
-    assert lp.fuse_gru and lp.chain_ok
-    lp.err.fill_(2)
-    with pytest.warns(UserWarning, match="chain launch timed out"):
-        _, second = model(i1, i2, iters=4, test_mode=True)
-    assert lp.fuse_gru and not lp.chain_ok and int(lp.err.item()) == 0
-    assert torch.equal(second, first)                        # (chains are off by default: the same launches ran)
+    assert lp.fuse_gru
     lp.err.fill_(1)
     with pytest.warns(UserWarning, match="fused ConvGRU launch timed out"):
-        _, third = model(i1, i2, iters=4, test_mode=True)
-    assert not lp.fuse_gru and maxabs(third, first) <= 2e-4
+        _, second = model(i1, i2, iters=4, test_mode=True)
+    assert not lp.fuse_gru and int(lp.err.item()) == 0 and maxabs(second, first) <= 2e-4
+    lp.err.fill_(1)
+    with pytest.raises(_ffi.DktError, match="fused ConvGRU launch had been switched off"):
+        model(i1, i2, iters=4, test_mode=True)
 
 
 @torch.no_grad()
