@@ -102,9 +102,45 @@ class C8RangeJob(ctypes.Structure):
 #: DKT_STATUS_MAX_JOBS of include/dktstereo.h
 STATUS_MAX_JOBS = 8
 
+#: DKT_FANDE_MAX_B, DKT_FANDE_MAX_JOBS, DKT_FANDE_WS_DOUBLES_PER_IMAGE of include/dktstereo.h
+FANDE_MAX_B, FANDE_MAX_JOBS, FANDE_WS_DOUBLES_PER_IMAGE = 64, 2, 512
+
+
+class FandeJob(ctypes.Structure):
+    """dkt_fande_job of include/dktstereo.h."""
+    _fields_ = [("src", ctypes.c_void_p), ("src_bstride", ctypes.c_long), ("tgt", ctypes.c_void_p), ("tgt_bstride", ctypes.c_long),
+                ("valid", ctypes.c_void_p), ("valid_bstride", ctypes.c_long), ("out", ctypes.c_void_p), ("out_bstride", ctypes.c_long),
+                ("out_valid", ctypes.c_void_p), ("out_valid_bstride", ctypes.c_long), ("tau", ctypes.c_float),
+                ("filter", ctypes.c_int), ("ensemble", ctypes.c_int), ("clamp", ctypes.c_int),
+                ("clamp_max", ctypes.c_float), ("ens_prob", ctypes.c_float), ("rand", ctypes.c_float * FANDE_MAX_B)]
+
+
+#: DKT_LOSS_MAX_PRED, DKT_LOSS_RAFT, DKT_LOSS_GWC, DKT_LOSS_REC of include/dktstereo.h
+LOSS_MAX_PRED, LOSS_RAFT, LOSS_GWC, LOSS_REC = 64, 0, 1, 24
+
+
+class SeqLossDesc(ctypes.Structure):
+    """dkt_seq_loss_desc of include/dktstereo.h."""
+    _fields_ = [("pred", ctypes.c_void_p * LOSS_MAX_PRED), ("pred_bstride", ctypes.c_long * LOSS_MAX_PRED),
+                ("weight", ctypes.c_float * LOSS_MAX_PRED), ("n", ctypes.c_int), ("n_loss", ctypes.c_int),
+                ("kind", ctypes.c_int), ("ntargets", ctypes.c_int),
+                ("gt", ctypes.c_void_p * 2), ("gt_bstride", ctypes.c_long * 2),
+                ("valid", ctypes.c_void_p * 2), ("valid_bstride", ctypes.c_long * 2), ("max_flow", ctypes.c_float),
+                ("mask", ctypes.c_void_p * 2), ("loss", ctypes.c_void_p * 2), ("rec", ctypes.c_void_p),
+                ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int)]
+
+
+class SeqLossGrad(ctypes.Structure):
+    """dkt_seq_loss_grad of include/dktstereo.h."""
+    _fields_ = [("grad", ctypes.c_void_p * LOSS_MAX_PRED), ("grad_loss", ctypes.c_void_p * 2)]
+
 # name -> argtypes, mirrors include/dktstereo.h one to one
 SIGNATURES = {
     "dkt_loop_status": [ctypes.POINTER(C8RangeJob), _i, _vp, _l, _vp, _vp, _i, _vp],
+    "dkt_fande": [ctypes.POINTER(FandeJob), _i, _i, _i, _i, _vp, _i, _vp],
+    "dkt_seq_loss_ws_doubles": [_i, _i, _i, _i, _i],
+    "dkt_seq_loss": [ctypes.POINTER(SeqLossDesc), _vp, _i, _vp],
+    "dkt_seq_loss_bwd": [ctypes.POINTER(SeqLossDesc), ctypes.POINTER(SeqLossGrad), _i, _vp],
     "dkt_motion_front_c8": [ctypes.POINTER(MotionFrontDesc), _i, _vp],
     "dkt_resample_pair_c8": [ctypes.POINTER(ResampleC8Job), ctypes.POINTER(ResampleC8Job), _i, _vp],
     "dkt_gru_c8_flag_words": [_i, _i, _i],
@@ -187,7 +223,7 @@ SIGNATURES = {
     "dkt_interp_bilinear": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }
 #: entry points that do not return an int status
-RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long}
+RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long}
 
 #: DKT_E_UNSUPPORTED of include/dktstereo.h
 E_UNSUPPORTED = -7

@@ -658,6 +658,83 @@ typedef struct dkt_c8_range_job {
 int dkt_loop_status(const dkt_c8_range_job *jobs, int njobs, const float *finite_src, long finite_n, int *err_word,
                     unsigned *status, int device, void *stream);
 
+/* ---- DKT Filter-and-Ensemble (csrc/fande.hip) ----------------------------------------------------------------------
+ * Replaces FandE/__init__.py:4-39 (FandE_Ensemble, FandE_Filter) and the four calls of tools/ft_dkt.py:203-210 that
+ * chain them.  One job = one disparity map (B,1,H,W) filtered against the EMA teacher's output and/or ensembled with it:
+ *   filter = 0  Ensemble only (FandE/__init__.py:4-21): src ensembled against tgt under `valid`;
+ *   filter = 1  Filter, withprob=False (:24-27,36-37), then Ensemble under the filtered mask when ensemble = 1;
+ *   filter = 2  Filter, withprob=True (:24-35,38), same.  rand[b] = torch.rand((B,1))[b] drawn by the caller.
+ * ens_prob = fl32(random.random()) of the Ensemble call; clamp != 0 applies torch.clamp(offset, max=clamp_max).
+ * Every expression is evaluated in the reference's order with fp32 roundings: sqrt(d*d) < tau, products left to right,
+ * direction in {+1,-1,0} (NaN -> 0), clamp propagates NaN.  The withprob ratio is fl32(sum vc) / fl32(sum valid) per image,
+ * the sums formed in fp64 (exact for 0/1 masks).  valid = NULL means valid == 1 (the pseudo label's, never materialised).
+ * out: AUG source (B,1,H,W); out_valid (filter != 0): the filtered mask (B,H,W).  All planes H x W contiguous, batch
+ * strides in elements.  ws: DKT_FANDE_WS_DOUBLES_PER_IMAGE * B * njobs doubles (caller-allocated, only read back by the
+ * same call).  Launches: one count pass when a job has filter = 2, then one apply pass for all jobs.
+ * Errors: null jobs / a null pointer a job needs / null ws DKT_E_NULL; njobs outside 1..DKT_FANDE_MAX_JOBS, B, H or W <= 0
+ * DKT_E_SHAPE; B > DKT_FANDE_MAX_B or an unknown filter mode DKT_E_UNSUPPORTED. */
+#define DKT_FANDE_MAX_B 64
+#define DKT_FANDE_MAX_JOBS 2
+#define DKT_FANDE_WS_DOUBLES_PER_IMAGE 512
+typedef struct dkt_fande_job {
+    const float *src; long src_bstride;
+    const float *tgt; long tgt_bstride;
+    const float *valid; long valid_bstride;     /* NULL: valid == 1 */
+    float *out; long out_bstride;
+    float *out_valid; long out_valid_bstride;   /* filter != 0 */
+    float tau;
+    int filter, ensemble, clamp;
+    float clamp_max, ens_prob;
+    float rand[DKT_FANDE_MAX_B];
+} dkt_fande_job;
+int dkt_fande(const dkt_fande_job *jobs, int njobs, int B, int H, int W, double *ws, int device, void *stream);
+
+/* ---- stereo sequence losses (csrc/stereo_loss.hip) -------------------------------------------------------------------
+ * Replaces sequence_loss_raft (meta_arch/raft_stereo/loss.py:3-40) and loss_gwcnet (meta_arch/gwcnet/gwc_loss.py:5-31)
+ * for one or two targets against the same predictions (tools/ft_dkt.py:227-228 calls the loss twice).
+ * Per target k: mask = (valid >= 0.5) & (sqrt(gt*gt) < max_flow), written as bool (B,1,H,W) contiguous;
+ *   kind DKT_LOSS_RAFT: mean_i = mean |p_i - gt| over the mask; kind DKT_LOSS_GWC: mean smooth-L1 (beta = 1);
+ *   loss_k = sum_{i < n_loss} weight[i] * mean_i, accumulated in fp32 in order i = 0 .. n_loss-1 (weight[i] already fp32).
+ * Sums are fp64 per-block partials reduced in a fixed order by a finalize launch: bit-identical from run to run, no atomics.
+ * rec (DKT_LOSS_REC doubles), written by the finalize launch:
+ *   rec[8k + 0] = number of mask pixels N_k   rec[8k + 1] = fl32 EPE mean of prediction n-1 over the mask
+ *   rec[8k + 2..4] = fl32 fractions of EPE < 1, 3, 5   rec[8k + 5] = 1 when gt is +-Inf on a mask pixel (loss.py:17)
+ *   rec[16] = 1 when some prediction holds a NaN and no Inf (loss.py:22, over the whole tensor)
+ * pred[i]: (B,1,H,W) with H x W planes contiguous and batch stride pred_bstride[i] (views such as [:, :1] are read in
+ * place).  gt, valid: (B,1,H,W) / (B,H,W) with batch strides.  ws: dkt_seq_loss_ws_doubles(ntargets, n, B, H, W) doubles.
+ * Two launches (partials, finalize); no host synchronisation.
+ * Errors: null desc / ws / a pointer the call needs DKT_E_NULL; B, H, W <= 0, n outside 1..DKT_LOSS_MAX_PRED, n_loss
+ * outside 1..n or ntargets outside 1..2 DKT_E_SHAPE; an unknown kind DKT_E_UNSUPPORTED. */
+#define DKT_LOSS_MAX_PRED 64
+#define DKT_LOSS_RAFT 0
+#define DKT_LOSS_GWC 1
+#define DKT_LOSS_REC 24
+typedef struct dkt_seq_loss_desc {
+    const float *pred[DKT_LOSS_MAX_PRED];
+    long pred_bstride[DKT_LOSS_MAX_PRED];
+    float weight[DKT_LOSS_MAX_PRED];
+    int n, n_loss, kind, ntargets;
+    const float *gt[2]; long gt_bstride[2];
+    const float *valid[2]; long valid_bstride[2];
+    float max_flow;
+    unsigned char *mask[2];                     /* out */
+    float *loss[2];                             /* out, device scalars */
+    double *rec;                                /* out */
+    int B, H, W;
+} dkt_seq_loss_desc;
+long dkt_seq_loss_ws_doubles(int ntargets, int n, int B, int H, int W);
+int dkt_seq_loss(const dkt_seq_loss_desc *d, double *ws, int device, void *stream);
+/* Backward of dkt_seq_loss in ONE launch, after it on the same stream, reading its mask and rec on the device:
+ *   grad[i] = sum_k [mask_k] * (RAFT: fl(fl(g_k * weight[i]) / N_k) * sgn(p_i - gt_k);
+ *                               GWC:  smooth-L1 backward with norm fl32(1/N_k) and upstream fl(g_k * weight[i]))
+ * and exactly 0 off every mask and for i >= n_loss.  g_k = *grad_loss[k] (device scalars).  grad[i]: (B,1,H,W)
+ * contiguous.  Errors as dkt_seq_loss, plus a null grad pointer DKT_E_NULL. */
+typedef struct dkt_seq_loss_grad {
+    float *grad[DKT_LOSS_MAX_PRED];
+    const float *grad_loss[2];
+} dkt_seq_loss_grad;
+int dkt_seq_loss_bwd(const dkt_seq_loss_desc *d, const dkt_seq_loss_grad *g, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
