@@ -14,6 +14,9 @@ import numpy as np
 import pytest
 import torch
 
+from _train_ref import torch_raft_loss as _torch_raft_loss
+from _train_ref import torch_targets as _torch_targets
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -271,48 +274,9 @@ def test_loss_pair_one_synchronising_call():
 
 
 # ---- a tiny DKT step ----------------------------------------------------------------------------------------------------
-def _torch_targets(disp_gt, valid_gt, disp_pl, disp_t, tau_gt, tau_pl, clamp, rand, p_gt, p_pl):
-    """tools/ft_dkt.py:203-210 restated in torch with explicit draws."""
-    def consistent(s, t, tau):
-        return (torch.sqrt((t - s) * (t - s)) < tau).float()
-
-    def filt(s, t, v, tau, r=None):
-        vc = consistent(s, t, tau) * v
-        s = s * v
-        if r is not None:
-            ratio = vc.flatten(1).sum(-1) / v.flatten(1).sum(-1)
-            sel = (r.reshape(-1).to(ratio.device) < ratio).float().reshape(-1, 1, 1, 1)
-            vc = (vc + (1 - vc) * (sel * (1 - vc) * v)) * v
-        return s * vc, vc
-
-    def ens(s, t, v, tau, p, c):
-        vc = consistent(s, t, tau) * v
-        s, t = s * v, t * v
-        off = p * torch.sqrt((s - t) * (s - t))
-        if c:
-            off = torch.clamp(off, max=c)
-        d = (s < t).float() - (s > t).float()
-        return (s + d * off * vc) * v
-
-    gt_f, vgt = filt(disp_gt, disp_t, valid_gt[:, None], tau_gt, rand)
-    gt_aug = ens(gt_f, disp_t, vgt, tau_gt, p_gt, clamp)
-    pl_f, vpl = filt(disp_pl, disp_t, torch.ones_like(disp_pl), tau_pl)
-    pl_aug = ens(pl_f, disp_t, vpl, tau_pl, p_pl, False)
-    return gt_aug, vgt[:, 0], pl_aug, vpl[:, 0]
-
-
-def _torch_raft_loss(preds, gt, valid, gamma=0.9, max_flow=700):
-    mask = ((valid >= 0.5) & (torch.sqrt(gt[:, 0] * gt[:, 0]) < max_flow))[:, None]
-    n = len(preds)
-    total = 0.0
-    for i, p in enumerate(preds):
-        total = total + (gamma ** (15 / (n - 1))) ** (n - i - 1) * (p - gt).abs()[mask].mean()
-    return total
-
-
 def test_dkt_step_end_to_end():
     """Teacher (library test_mode) -> fande_targets -> RAFT student (3 iterations, 64 x 128, under autograd) ->
-    dkt_loss_pair -> parameter gradients, against the same student tensors through this file's torch restatement."""
+    dkt_loss_pair -> parameter gradients, against the same student tensors through the torch restatement of _train_ref.py."""
     import _cases
     import _synth
     from dkt_stereo_amd.fande import fande_targets

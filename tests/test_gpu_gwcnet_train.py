@@ -50,15 +50,25 @@ _STEP = {}
 
 
 def train_step(golden, name):
-    """One reference-style step (forward in train(), loss, backward), cached per case."""
+    """One reference-style step (forward in train(), loss, backward), cached per case.
+
+    The 2-D and 3-D layers run on the vendor library, whose default algorithm choice is not deterministic: from run to
+    run the loss moved in its 7th digit and the gwc case's dres0.0.0.weight gradient ranged from 5e-3 to 2.5e-2 of its
+    max away from the fixture.  With deterministic algorithm selection, forward and backward included, repeated runs
+    gave the same loss and predictions and gradients within 1e-2 of the fixture, so the step is measured that way."""
     if name not in _STEP:
         g = golden("gwcnet_train")
         i1, i2, gt, valid, cat, stride = inputs(g, name)
         model = make_model(cat).train()
-        res = model(i1, i2)
-        loss = loss_gwcnet(res["disp_preds"], gt, valid)
-        loss.backward()
-        torch.cuda.synchronize()
+        was = torch.backends.cudnn.deterministic
+        torch.backends.cudnn.deterministic = True
+        try:
+            res = model(i1, i2)
+            loss = loss_gwcnet(res["disp_preds"], gt, valid)
+            loss.backward()
+            torch.cuda.synchronize()
+        finally:
+            torch.backends.cudnn.deterministic = was
         _STEP[name] = (g, model, res, loss, stride)
     return _STEP[name]
 

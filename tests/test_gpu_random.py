@@ -30,7 +30,7 @@ def same(a, b):
 
 @settings(**SET)
 @given(B=st.integers(1, 3), C=st.integers(1, 40), H=st.integers(1, 5), W1=st.integers(2, 70), dW=st.integers(-8, 12),
-       L=st.integers(1, 4), r=st.integers(0, 5), seed=st.integers(0, 10 ** 6))
+       L=st.integers(1, 4), r=st.integers(0, 8), seed=st.integers(0, 10 ** 6))
 @torch.no_grad()
 def test_corr_block_random(c_oracle, B, C, H, W1, dW, L, r, seed):
     from dkt_stereo_amd.corr import CorrBlock1D, _lookup
