@@ -90,11 +90,15 @@ def pack(x, dst=None, ch0=0, scale=None):
 
 
 def unpack(a, C=None, ch0=0):
+    """Channels [ch0, ch0 + C) of an ActC8 -> fp32 NCHW, every channel decoded with its own scale (`channel_scales`)."""
     C = a.C - ch0 if C is None else C
     y = torch.empty((a.B, C, a.H, a.W), device=a.device, dtype=torch.float32)
     rc = _ffi.lib().dkt_act_c8_unpack(a.data_ptr(), a.bstride_bytes, y.data_ptr(), y.stride(0), a.B, C, a.H, a.W, ch0,
                                       a.scale, _ffi.device_of(y), _ffi.stream_of(y))
     _ffi.check(rc, "dkt_act_c8_unpack")
+    t0 = a.C - a.tail - ch0                  # first tail channel of y
+    if a.tail and a.tail_scale != a.scale and t0 < C:
+        y[:, max(t0, 0):] *= a.scale / a.tail_scale          # (the kernel divided by a.scale; powers of two: exact)
     return y
 
 
@@ -456,6 +460,8 @@ def desc(srcs, layer, relu=False, out=None, out_c8=None, out_c8_ch0=0, epilogue=
             setattr(d, name, a.data_ptr())
             setattr(d, name + "_bstride", a.bstride_bytes)
             setattr(d, name + "_ch0", c0)
+            if name == "out2_c8" and out_c8 is not None and out_c8.scale != a.scale:
+                raise ValueError("conv2d_c8: one act_scale per launch, the C8S destinations carry %g and %g" % (out_c8.scale, a.scale))
             d.act_scale = a.scale
             if name == "out_c8" and tail is not None and a.tail:
                 if a.tail != int(tail.shape[1]) or c0 + int(layer.weight.shape[0]) + a.tail != a.C:

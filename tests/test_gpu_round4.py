@@ -35,16 +35,7 @@ def _make(B, H, W, xch, seed, ctx_scale=1.0):
     return gru, h, xs, cz, cr, cq
 
 
-def _ref64(gru, h, xs, cz, cr, cq):
-    """core/update.py:23-32 in fp64."""
-    p = {k: v.double() for k, v in gru.state_dict().items()}
-    h, cz, cr, cq = h.double(), cz.double(), cr.double(), cq.double()
-    x = torch.cat([t.double() for t in xs], 1)
-    hx = torch.cat([h, x], 1)
-    z = torch.sigmoid(F.conv2d(hx, p["convz.weight"], p["convz.bias"], padding=1) + cz)
-    r = torch.sigmoid(F.conv2d(hx, p["convr.weight"], p["convr.bias"], padding=1) + cr)
-    q = torch.tanh(F.conv2d(torch.cat([r * h, x], 1), p["convq.weight"], p["convq.bias"], padding=1) + cq)
-    return (1 - z) * h + z * q
+from _c8_ref import gru_ref64 as _ref64          # core/update.py:23-32 in fp64 (shared with the scaled-operand tests)
 
 
 class _State:
