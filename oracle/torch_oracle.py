@@ -260,6 +260,9 @@ def _norm(sd, name, x, kind):
                             sd[name + '.weight'], sd[name + '.bias'], False, 0.1, 1e-5)
     if kind == 'none':
         return x
+    if kind == 'group':
+        # core/extractor.py:17-22, :130-131: num_groups = planes // 8 in the blocks, 8 for the 64-channel stem (the same number)
+        return F.group_norm(x, x.shape[1] // 8, sd[name + '.weight'], sd[name + '.bias'], 1e-5)
     raise ValueError(kind)
 
 
@@ -288,8 +291,18 @@ def basic_encoder(sd, pre, x, kind='instance', downsample=2):
     return _conv(sd, pre + '.conv2', _trunk(sd, pre, x, kind, downsample))
 
 
-def multi_encoder(sd, pre, x, kind='batch', downsample=2, num_layers=3, n_heads=2):
+def multi_encoder(sd, pre, x, kind='batch', downsample=2, num_layers=3, n_heads=2, dual_inp=False):
+    """dual_inp (core/extractor.py:280-282, :298-299): the heads see the first half of the batch, the trunk's output on the
+    whole batch is appended to the returned scales."""
     x = _trunk(sd, pre, x, kind, downsample)
+    if dual_inp:
+        v = x
+        return multi_heads(sd, pre, x[:x.shape[0] // 2], kind, num_layers, n_heads) + (v,)
+    return multi_heads(sd, pre, x, kind, num_layers, n_heads)
+
+
+def multi_heads(sd, pre, x, kind='batch', num_layers=3, n_heads=2):
+    """core/extractor.py:284-296: the output heads of the trunk's result x, with layer4 / layer5 between the scales."""
     o08 = [_conv(sd, '%s.outputs08.%d.1' % (pre, j), _res_block(sd, '%s.outputs08.%d.0' % (pre, j), x, kind, 1))
            for j in range(n_heads)]
     if num_layers == 1:
