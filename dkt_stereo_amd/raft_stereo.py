@@ -34,6 +34,7 @@ from .update import (FUSE_GATES, GPU_GUARD, BasicMultiUpdateBlock, _side_stream,
                      pool2x, replay_graph)
 from . import conv as _conv
 from . import extractor as _extractor
+from . import upsample as _upsample
 from .utils import coords_grid
 
 #: configs/raft_stereo/base.json of the reference
@@ -466,11 +467,18 @@ class RAFTStereo(nn.Module):
             return None
         return net, buf
 
-    def upsample_flow(self, flow, mask):
+    def upsample_flow(self, flow, mask, channels=None):
         """raft_stereo.py:70-82, convex combination over a 3x3 neighbourhood: one fused kernel
-        (dkt_convex_upsample) on the GPU inference path, the reference's op sequence otherwise."""
+        (dkt_convex_upsample) on the GPU inference path, the autograd node of upsample.py (same bits, HIP backward) for
+        fp32 GPU tensors that need a gradient, the reference's op sequence otherwise.  `channels` = c returns the leading
+        c channels, upsample_flow(flow, mask)[:, :c]; the node computes only those."""
         N, D, H, W = flow.shape
         factor = 2 ** self.args.n_downsample
+        if (flow.is_cuda and torch.is_grad_enabled() and (flow.requires_grad or mask.requires_grad)
+                and flow.dtype == mask.dtype == torch.float32):
+            return _upsample.convex_upsample(flow, mask, factor, channels)
+        if channels is not None:
+            return self.upsample_flow(flow, mask)[:, :channels]
         if flow.is_cuda and not (torch.is_grad_enabled() and (flow.requires_grad or mask.requires_grad)):
             flow = flow.float().contiguous()
             mask = mask.float().contiguous()
@@ -993,7 +1001,8 @@ class RAFTStereo(nn.Module):
             # stereo: project the update onto the epipolar line (raft_stereo.py:165), without writing into an autograd output
             delta_flow = torch.cat([delta_flow[:, :1], torch.zeros_like(delta_flow[:, 1:])], dim=1)
             coords1 = coords1 + delta_flow
-            predictions.append(self.upsample_flow(coords1 - coords0, up_mask)[:, :1])
+            # one channel straight from the node (channel 1 of the flow is identically zero): plain (N, 1, fH, fW) tensors
+            predictions.append(self.upsample_flow(coords1 - coords0, up_mask, channels=1))
         # the reference's return convention (raft_stereo.py:185-187): its loss reads results['disp_preds'] (loss.py:5,
         # tools/ft_dkt.py:218,262)
         return dict(disp_preds=predictions)

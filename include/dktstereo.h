@@ -120,6 +120,29 @@ int dkt_convex_upsample(const float *flow, const float *mask, float *out, int N,
 int dkt_context_upsample(const float *disp_low, const float *up_weights, float *out, int B, int h, int w,
                          int device, void *stream);
 
+/* The training path's upsample_flow (meta_arch/raft_stereo/raft_stereo.py:70-82 and, for the backward, torch autograd
+ * through those lines), once per refinement iteration of RAFTStereo.forward with test_mode=False (:168).
+ *
+ * Forward, the leading Dout <= D channels: out (N,Dout,f*H,f*W), bit-identical to dkt_convex_upsample(...)[:, :Dout]
+ * (the same operations in the same order per output).  factor in {1,2,4,8}. */
+int dkt_convex_upsample_fwd(const float *flow, const float *mask, float *out, int N, int D, int Dout, int H, int W,
+                            int factor, int device, void *stream);
+
+/* Backward.  gout (N,Dout,f*H,f*W): batch stride gout_bstride elements, the other dimensions contiguous.  With
+ * p_k = softmax_k(mask[n,(k*f+i)*f+j,h,w]) recomputed from the mask and v_{d,k} = f*flow[n,d,h+k/3-1,w+k%3-1]:
+ *   gmask[n,(k*f+i)*f+j,h,w] = p_k (a_k - sum_k' p_k' a_k'),   a_k = sum_{d<Dout} gout[n,d,f*h+i,f*w+j] v_{d,k}
+ *   gflow[n,d,y,x] = f * sum_k C[n,d,k,y-k/3+1,x-k%3+1],   C[n,d,k,h,w] = sum_{i,j} p_k(i,j,h,w) gout[n,d,f*h+i,f*w+j]
+ *   gflow[:, d >= Dout] = 0.
+ * gflow (N,D,H,W) or gmask (N,9*f*f,H,W) may be null (not wanted), not both.  ws: N*Dout*9*H*W floats of scratch, needed
+ * when gflow is wanted.  Deterministic (no atomics): C is summed over j ascending, then i ascending, gflow over k
+ * ascending.  One launch per two channels of Dout plus one for gflow.
+ * Errors (both entries): a null pointer the call needs DKT_E_NULL; N, D, H, W <= 0, factor < 1, Dout outside 1..D or a
+ * batch stride shorter than one image DKT_E_SHAPE; another factor, N or D > 65535 or H*W > 2^31 - 257 DKT_E_UNSUPPORTED;
+ * out / gout not aligned to min(4*f, 16) bytes or gout_bstride not a multiple of f DKT_E_ALIGN. */
+int dkt_convex_upsample_bwd(const float *gout, long gout_bstride, const float *flow, const float *mask, float *gflow,
+                            float *gmask, float *ws, int N, int D, int Dout, int H, int W, int factor, int device,
+                            void *stream);
+
 /* ---- backward of lookup / pyramid (autograd of core/corr.py:119-146) -------- */
 
 /* Gradient of every pyramid level from the gradient of one lookup's output:
