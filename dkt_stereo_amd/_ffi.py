@@ -197,6 +197,10 @@ SIGNATURES = {
     "dkt_gwc_concat_volume_bwd": [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_gru_gate_zr": [_vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _l, _i, _vp],
     "dkt_gru_gate_out": [_vp, _vp, _l, _vp, _vp, _l, _vp, _l, _i, _i, _l, _i, _vp],
+    "dkt_gru_gate_zr_train": [_vp, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _l, _i, _vp],
+    "dkt_gru_gate_out_train": [_vp, _vp, _l, _vp, _vp, _l, _vp, _vp, _l, _i, _i, _l, _i, _vp],
+    "dkt_gru_gate_out_bwd": [_vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _l, _i, _vp],
+    "dkt_gru_gate_zr_bwd": [_vp, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _l, _i, _vp],
     "dkt_conv2d_packed_elems": [_ip, _i, _i, _i, _i],
     "dkt_conv2d_pack_weights": [_vp, _ip, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp],
     "dkt_conv2d_f16s": [_pp, _ip, _lp, _i, _vp, _vp, _vp, _f, _f, _vp, _l,
@@ -223,6 +227,8 @@ SIGNATURES = {
     "dkt_ema_update": [_vp, _vp, _vp, _i, _f, _f, _vp, _i, _vp],
     "dkt_pool2x": [_vp, _vp, _l, _i, _i, _i, _vp],
     "dkt_interp_bilinear": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
+    "dkt_pool2x_bwd": [_vp, _vp, _l, _i, _i, _i, _vp],
+    "dkt_interp_bilinear_bwd": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }
 #: entry points that do not return an int status
 RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long}

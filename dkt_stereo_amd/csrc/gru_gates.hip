@@ -9,11 +9,7 @@
 // rh is stored straight into the first Ch channels of convq's [r*h | x] input
 // buffer, so the second torch.cat of the reference never happens.
 // HBM-bound: float4 accesses, grid-stride, ~2048 blocks.
-#include "dkt_common.h"
-
-__device__ __forceinline__ float dkt_sigmoid(float x) {
-    return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x)));
-}
+#include "gru_gates.h"     // dkt_sigmoid, dkt_gru_out: shared with gru_gates_train.hip
 
 struct GateZrArgs {
     const float *azr, *cz, *cr, *h;
@@ -56,15 +52,6 @@ __global__ __launch_bounds__(256) void gru_gate_zr_kernel(GateZrArgs a) {
     }
 }
 
-static inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
-static unsigned gate_blocks(long total) {
-    long blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
-
 extern "C" int dkt_gru_gate_zr(const float *azr, const float *cz, long cz_bstride,
                                const float *cr, long cr_bstride, const float *h, long h_bstride,
                                float *z, float *rh, long rh_bstride,
@@ -77,15 +64,15 @@ extern "C" int dkt_gru_gate_zr(const float *azr, const float *cz, long cz_bstrid
     a.cz_bs = cz_bstride; a.cr_bs = cr_bstride; a.h_bs = h_bstride; a.rh_bs = rh_bstride;
     a.CHW = (long)Ch * HW;
     const bool vec = (a.CHW % 4 == 0) && (cz_bstride % 4 == 0) && (cr_bstride % 4 == 0) &&
-                     (h_bstride % 4 == 0) && (rh_bstride % 4 == 0) && aligned16(azr) && aligned16(cz) &&
-                     aligned16(cr) && aligned16(h) && aligned16(z) && aligned16(rh);
+                     (h_bstride % 4 == 0) && (rh_bstride % 4 == 0) && dkt_aligned16(azr) && dkt_aligned16(cz) &&
+                     dkt_aligned16(cr) && dkt_aligned16(h) && dkt_aligned16(z) && dkt_aligned16(rh);
     hipStream_t st = (hipStream_t)stream;
     if (vec) {
         a.total4 = (long)B * a.CHW / 4;
-        hipLaunchKernelGGL(gru_gate_zr_kernel<4>, dim3(gate_blocks(a.total4)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(gru_gate_zr_kernel<4>, dim3(dkt_gate_blocks(a.total4)), dim3(256), 0, st, a);
     } else {
         a.total4 = (long)B * a.CHW;
-        hipLaunchKernelGGL(gru_gate_zr_kernel<1>, dim3(gate_blocks(a.total4)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(gru_gate_zr_kernel<1>, dim3(dkt_gate_blocks(a.total4)), dim3(256), 0, st, a);
     }
     return dkt_launch_status();
 }
@@ -97,12 +84,6 @@ struct GateOutArgs {
     long CHW;
     long total4;
 };
-
-__device__ __forceinline__ float dkt_gru_out(float aq, float cq, float z, float h) {
-    const float q = tanhf(__fadd_rn(aq, cq));
-    // (1-z)*h + z*q, two rounded products and a rounded sum (core/update.py:31)
-    return __fadd_rn(__fmul_rn(__fsub_rn(1.0f, z), h), __fmul_rn(z, q));
-}
 
 template <int V>
 __global__ __launch_bounds__(256) void gru_gate_out_kernel(GateOutArgs a) {
@@ -142,15 +123,15 @@ extern "C" int dkt_gru_gate_out(const float *aq, const float *cq, long cq_bstrid
     a.cq_bs = cq_bstride; a.h_bs = h_bstride; a.hout_bs = hout_bstride;
     a.CHW = (long)Ch * HW;
     const bool vec = (a.CHW % 4 == 0) && (cq_bstride % 4 == 0) && (h_bstride % 4 == 0) &&
-                     (hout_bstride % 4 == 0) && aligned16(aq) && aligned16(cq) && aligned16(z) &&
-                     aligned16(h) && aligned16(hout);
+                     (hout_bstride % 4 == 0) && dkt_aligned16(aq) && dkt_aligned16(cq) && dkt_aligned16(z) &&
+                     dkt_aligned16(h) && dkt_aligned16(hout);
     hipStream_t st = (hipStream_t)stream;
     if (vec) {
         a.total4 = (long)B * a.CHW / 4;
-        hipLaunchKernelGGL(gru_gate_out_kernel<4>, dim3(gate_blocks(a.total4)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(gru_gate_out_kernel<4>, dim3(dkt_gate_blocks(a.total4)), dim3(256), 0, st, a);
     } else {
         a.total4 = (long)B * a.CHW;
-        hipLaunchKernelGGL(gru_gate_out_kernel<1>, dim3(gate_blocks(a.total4)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(gru_gate_out_kernel<1>, dim3(dkt_gate_blocks(a.total4)), dim3(256), 0, st, a);
     }
     return dkt_launch_status();
 }

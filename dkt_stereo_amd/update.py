@@ -17,7 +17,8 @@ What differs from the reference is how a GRU step is evaluated (core/update.py:2
   * FUSE_GATES = False or the vendor-convolution backend: two streaming gate kernels
     (dkt_gru_gate_zr / _out) after the convolutions instead of ~12 elementwise launches.
 Convolutions go through ``dkt_stereo_amd.conv.conv2d`` (see that module).
-Inference only.
+Under autograd (training) the block runs ``conv.conv2d_autograd`` nodes and, for fp32 tensors on a HIP device, the gate and
+resampler nodes of ``gru_train`` (``BasicMultiUpdateBlock.TRAIN_NODES``); every other entry point here is inference only.
 """
 import contextlib
 import gc
@@ -31,7 +32,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _ffi
+from . import _ffi, gru_train
 from .conv import (_CACHE_LOCK, conv2d, conv2d_accumulate, conv2d_gate_out, conv2d_gate_out_pair, conv2d_gate_zr,
                    conv2d_autograd, conv2d_gate_zr_pair, conv2d_pair, few_eligible, get_backend, hip_eligible, pair_eligible)
 
@@ -611,13 +612,24 @@ class BasicMultiUpdateBlock(nn.Module):
         ts = [t for t in list(net) + [t for scale in inp for t in scale] + [corr, aux] if torch.is_tensor(t)]
         return any(t.requires_grad for t in ts) or any(p.requires_grad for p in self.parameters())
 
-    @staticmethod
-    def _gru_autograd(gru, h, cz, cr, cq, *xs):
+    #: training path: the gates and the two resamplers run as this library's autograd nodes (gru_train) when the tensors
+    #: are fp32 on a HIP device; False = the torch expression sequence (the A/B handle of tools/bench_gru_train.py)
+    TRAIN_NODES = True
+
+    @classmethod
+    def _train_nodes(cls, *ts):
+        return cls.TRAIN_NODES and all(t.is_cuda and t.dtype == torch.float32 for t in ts)
+
+    @classmethod
+    def _gru_autograd(cls, gru, h, cz, cr, cq, *xs):
         """core/update.py:23-32 on differentiable convolutions (conv.conv2d_autograd); z and r share one convolution."""
         hx = torch.cat([h, *xs], dim=1)
         zr = SimpleNamespace(weight=torch.cat([gru.convz.weight, gru.convr.weight], 0),
                              bias=torch.cat([gru.convz.bias, gru.convr.bias], 0), padding=gru.convz.padding)
         a = conv2d_autograd(hx, zr)
+        if cls._train_nodes(a, h, cz, cr, cq, *xs):
+            z, rh = gru_train.gate_zr(a, cz, cr, h)
+            return gru_train.gate_out(conv2d_autograd(torch.cat([rh, *xs], dim=1), gru.convq), cq, z, h)
         ch = h.shape[1]
         z = torch.sigmoid(a[:, :ch] + cz)
         r = torch.sigmoid(a[:, ch:] + cr)
@@ -639,8 +651,12 @@ class BasicMultiUpdateBlock(nn.Module):
         fine, mid, coarse = grus
         it_fine, it_mid, it_coarse = flags
         net = list(net)
-        p2 = lambda t: F.avg_pool2d(t, 3, stride=2, padding=1)
-        up = lambda t, dest: F.interpolate(t, dest.shape[2:], mode="bilinear", align_corners=True)
+        if self._train_nodes(*net):
+            p2 = gru_train.pool2x
+            up = lambda t, dest: gru_train.interp(t, dest.shape[2:])
+        else:
+            p2 = lambda t: F.avg_pool2d(t, 3, stride=2, padding=1)
+            up = lambda t, dest: F.interpolate(t, dest.shape[2:], mode="bilinear", align_corners=True)
         if it_coarse:
             net[2] = self._gru_autograd(coarse, net[2], *inp[2], p2(net[1]))
         if it_mid:

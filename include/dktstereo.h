@@ -284,6 +284,42 @@ int dkt_gru_gate_out(const float *aq, const float *cq, long cq_bstride,
                      float *hout, long hout_bstride,
                      int B, int Ch, long HW, int device, void *stream);
 
+/* The same two stages on the training path (BasicMultiUpdateBlock under autograd; core/update.py:23-32 ==
+ * meta_arch/igev_stereo/update.py:33-41, and torch autograd through those lines for the two backward entries).
+ *
+ * Forward: the arithmetic of dkt_gru_gate_zr / dkt_gru_gate_out plus the one plane the backward needs: r, q (dense
+ * (B,Ch,HW)).  z, rh and hout are bit-identical to what dkt_gru_gate_zr / dkt_gru_gate_out write from the same inputs. */
+int dkt_gru_gate_zr_train(const float *azr, const float *cz, long cz_bstride,
+                          const float *cr, long cr_bstride, const float *h, long h_bstride,
+                          float *z, float *r, float *rh, long rh_bstride,
+                          int B, int Ch, long HW, int device, void *stream);
+int dkt_gru_gate_out_train(const float *aq, const float *cq, long cq_bstride,
+                           const float *z, const float *h, long h_bstride,
+                           float *q, float *hout, long hout_bstride,
+                           int B, int Ch, long HW, int device, void *stream);
+
+/* Backward of the second stage, one launch.  gout: the gradient of h' (batch stride gout_bstride); z, q: dense, as the
+ * forward wrote them; h with its batch stride.  Dense (B,Ch,HW) outputs, each may be null (not wanted), not all three:
+ *   gaq = (gout*z)*(1 - q*q)   (the gradient of aq and of cq)
+ *   gz  = gout*(q - h)
+ *   gh  = gout*(1 - z)
+ * Every product and difference rounded once, in the order written. */
+int dkt_gru_gate_out_bwd(const float *gout, long gout_bstride, const float *z, const float *q,
+                         const float *h, long h_bstride, float *gaq, float *gz, float *gh,
+                         int B, int Ch, long HW, int device, void *stream);
+
+/* Backward of the first stage, one launch.  gz: the gradient of z (dense); grh: the gradient of rh (batch stride
+ * grh_bstride); z, r: dense, as the forward wrote them.  gazr (B,2Ch,HW) dense: the gradient of the merged z|r
+ * pre-activation (its halves are the gradients of cz and cr); gh (B,Ch,HW) dense.  Either may be null, not both:
+ *   gazr[:, :Ch] = (gz*z)*(1 - z)
+ *   gazr[:, Ch:] = ((grh*h)*r)*(1 - r)
+ *   gh           = grh*r
+ * All four entries: a null pointer the call needs DKT_E_NULL; B, Ch or HW <= 0 DKT_E_SHAPE.  16-byte accesses when
+ * Ch*HW, every batch stride and every pointer allow it, 4-byte ones otherwise. */
+int dkt_gru_gate_zr_bwd(const float *gz, const float *grh, long grh_bstride, const float *z, const float *r,
+                        const float *h, long h_bstride, float *gazr, float *gh,
+                        int B, int Ch, long HW, int device, void *stream);
+
 /* ---- update-operator convolutions ------------------------------------------------ */
 
 /* Correlation lookup fused with the 1x1 convolution that consumes it: core/corr.py:127-146
@@ -435,6 +471,20 @@ int dkt_conv2d_direct_accumulate_diff(const float *x, long x_bstride, const floa
 int dkt_pool2x(const float *x, float *y, long planes, int H, int W, int device, void *stream);
 int dkt_interp_bilinear(const float *x, float *y, long planes, int H, int W, int Ho, int Wo,
                         int device, void *stream);
+
+/* Their gradients on the training path (torch autograd through core/update.py:87-96), `planes` contiguous planes,
+ * one owner thread per input element, no atomics: bit-identical from run to run.
+ *   dkt_pool2x_bwd: gy (planes,Ho,Wo) with Ho = (H-1)/2+1, Wo = (W-1)/2+1 -> gx (planes,H,W);
+ *     gx[iy,ix] = sum of fl(gy[oy,ox]/9) over the windows that hold (iy,ix) (|2 oy - iy| <= 1, |2 ox - ix| <= 1: at
+ *     most 4), in ascending (oy,ox).
+ *   dkt_interp_bilinear_bwd: gy (planes,Ho,Wo) -> gx (planes,H,W); gx[iy,ix] = sum gy[oy,ox]*wy*wx with the forward's own
+ *     fp32 weights (fy = fl(sy*oy), y0 = (int)fy, y1 = y0 + (y0 < H-1), ly1 = fl(fy - y0), ly0 = fl(1 - ly1): row oy
+ *     gives ly0 to y0 and ly1 to y1; columns alike), each term fl(fl(wy*wx)*gy), in ascending (oy, tap, ox, tap).  An
+ *     input element no output reads gets 0.
+ * Errors: null pointer DKT_E_NULL; a size <= 0 DKT_E_SHAPE; H*W or Ho*Wo beyond int, Ho or Wo > 2^22 DKT_E_UNSUPPORTED. */
+int dkt_pool2x_bwd(const float *gy, float *gx, long planes, int H, int W, int device, void *stream);
+int dkt_interp_bilinear_bwd(const float *gy, float *gx, long planes, int H, int W, int Ho, int Wo,
+                            int device, void *stream);
 
 /* Encoder glue (core/extractor.py:47-60,176-178; not on the scoped hot path, but inside the
  * timed forward): InstanceNorm2d(affine=False) with optional fused ReLU over `planes` = N*C

@@ -1,0 +1,208 @@
+#!/usr/bin/env python3
+"""The update operator alone on the training path (BasicMultiUpdateBlock under autograd, tools/ft_dkt.py:223-242 of the
+reference) at the recipe shape of run_scripts/raft-stereo/ft_booster.sh: B = 2, 480 x 896 images, i.e. a 120 x 224 finest
+level, 3 GRU layers, 16 calls chained through the hidden states, forward and backward with a scalar loss on the 16 flow
+updates and masks; the weights are trainable (their gradient is the vendor library's in both arms).
+
+  arm a  BasicMultiUpdateBlock.TRAIN_NODES = False: gates and resamplers as torch's expression sequence (training before
+         the nodes);
+  arm b  TRAIN_NODES = True: gru_train.gate_zr / gate_out / pool2x / interp (dkt_gru_gate_*_train, dkt_gru_gate_*_bwd,
+         dkt_pool2x_bwd, dkt_interp_bilinear_bwd).
+
+The arms alternate in one process after warm-up.  Per arm: wall ms of a step (host clock around a step that ends in a
+synchronise; median and minimum) and torch.cuda.max_memory_allocated over a step.  "raw_calls": every new entry at the
+finest level's shape issued back to back through the C ABI on one stream, buffer sets in rotation (past the 256 MiB
+Infinity Cache), HIP events around the calls, median of 5: us per call and the fraction of 8 TB/s its compulsory bytes
+would take.  Launch counts and kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of `--arms a` /
+`--arms b`.
+
+    python tools/bench_gru_train.py [--steps 10] [--warmup 3] [--arms a,b] [--no-raw]
+    python tools/bench_gru_train.py --sweep     worst error of the device's sigmoid (dkt_sigmoid) and tanhf against float64
+                                                on linspace(-30, 30, 4 000 001): the E_sigma / E_t of tests/_gru_ref.py
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from dkt_stereo_amd import _ffi  # noqa: E402
+from dkt_stereo_amd.update import BasicMultiUpdateBlock  # noqa: E402
+
+PEAK_BPS = 8e12
+B, H, W, CH, ITERS = 2, 480 // 4, 896 // 4, 128, 16
+
+
+def make_block():
+    cfg = dict(corr_levels=4, corr_radius=4, n_downsample=2, n_gru_layers=3, hidden_dims=[CH, CH, CH], slow_fast_gru=False)
+    torch.manual_seed(0)
+    return BasicMultiUpdateBlock(SimpleNamespace(**cfg), hidden_dims=cfg["hidden_dims"]).cuda()
+
+
+def make_inputs(seed=1):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g)
+    net0 = [torch.tanh(r(B, CH, H >> i, W >> i)).cuda() for i in range(3)]
+    # the context features as the model hands them over: three channel slices of one tensor per scale (raft_stereo.py:114)
+    inp = [list((0.5 * r(B, 3 * CH, H >> i, W >> i)).cuda().split(CH, dim=1)) for i in range(3)]
+    corr, flow = r(B, 36, H, W).cuda(), r(B, 2, H, W).cuda()
+    wd = [r(B, 2, H, W).cuda() for _ in range(ITERS)]
+    wm = [r(B, 144, H, W).cuda() for _ in range(ITERS)]
+    return net0, inp, corr, flow, wd, wm
+
+
+def compulsory_planes():
+    """(B, Ch, HW) planes each entry must move at least (read + written), at the finest level."""
+    return {"dkt_gru_gate_zr_train": 5 + 3,      # azr (2), cz, cr, h -> z, r, rh
+            "dkt_gru_gate_out_train": 4 + 2,     # aq, cq, z, h -> q, h'
+            "dkt_gru_gate_out_bwd": 4 + 3,       # g, z, q, h -> gaq, gz, gh
+            "dkt_gru_gate_zr_bwd": 5 + 3,        # gz, grh, z, r, h -> gazr (2), gh
+            "dkt_pool2x_bwd": 0.25 + 1,          # gy at half resolution -> gx
+            "dkt_interp_bilinear_bwd": 1 + 0.25}  # gy at the finest level -> gx at half resolution
+
+
+def raw_calls(sets=4, rounds=6, reps=5):
+    lib = _ffi.lib()
+    HW = H * W
+    n = CH * HW
+    plane = lambda k=1: torch.randn(B, k * CH, H, W, device="cuda")
+    unit = lambda: torch.rand(B, CH, H, W, device="cuda")
+    half = lambda: torch.randn(B, CH, H // 2, W // 2, device="cuda")
+    bufs = [dict(azr=plane(2), a=plane(), b=plane(), c=plane(), h=plane(), z=unit(), r=unit(), q=unit() * 2 - 1,
+                 o1=plane(), o2=plane(), o3=plane(), o4=plane(2), small=half(), small_o=half()) for _ in range(sets)]
+    dev, st = _ffi.device_of(bufs[0]["a"]), _ffi.stream_of(bufs[0]["a"])
+    p = lambda t: t.data_ptr()
+    calls = {
+        "dkt_gru_gate_zr_train": lambda t: lib.dkt_gru_gate_zr_train(p(t["azr"]), p(t["a"]), n, p(t["b"]), n, p(t["h"]), n, p(t["o1"]),
+                                                                     p(t["o2"]), p(t["o3"]), n, B, CH, HW, dev, st),
+        "dkt_gru_gate_out_train": lambda t: lib.dkt_gru_gate_out_train(p(t["a"]), p(t["b"]), n, p(t["z"]), p(t["h"]), n, p(t["o1"]),
+                                                                       p(t["o2"]), n, B, CH, HW, dev, st),
+        "dkt_gru_gate_out_bwd": lambda t: lib.dkt_gru_gate_out_bwd(p(t["a"]), n, p(t["z"]), p(t["q"]), p(t["h"]), n, p(t["o1"]),
+                                                                   p(t["o2"]), p(t["o3"]), B, CH, HW, dev, st),
+        "dkt_gru_gate_zr_bwd": lambda t: lib.dkt_gru_gate_zr_bwd(p(t["a"]), p(t["b"]), n, p(t["z"]), p(t["r"]), p(t["h"]), n,
+                                                                 p(t["o4"]), p(t["o1"]), B, CH, HW, dev, st),
+        "dkt_pool2x_bwd": lambda t: lib.dkt_pool2x_bwd(p(t["small"]), p(t["o1"]), B * CH, H, W, dev, st),
+        "dkt_interp_bilinear_bwd": lambda t: lib.dkt_interp_bilinear_bwd(p(t["a"]), p(t["small_o"]), B * CH, H // 2, W // 2, H, W,
+                                                                         dev, st),
+    }
+    out = {}
+    plane_bytes = B * n * 4
+    for name, fn in calls.items():
+        for t in bufs:
+            _ffi.check(fn(t), name)
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(rounds):
+                for t in bufs:
+                    fn(t)
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3 / (rounds * len(bufs)))
+        med = sorted(us)[len(us) // 2]
+        nbytes = compulsory_planes()[name] * plane_bytes
+        out[name] = {"us_per_call": round(med, 2), "compulsory_MB": round(nbytes / 1e6, 2),
+                     "frac_of_8TBps": round(nbytes / PEAK_BPS / (med * 1e-6), 3)}
+    return out
+
+
+def sweep():
+    """Worst error of dkt_sigmoid and tanhf (through the training entries: x + 0 is exact) in ulp of the true result and
+    relative to it in u = 2^-24."""
+    lib = _ffi.lib()
+    x = torch.linspace(-30.0, 30.0, 4000001, dtype=torch.float64).float()
+    n = x.numel()
+    xg = x.cuda()
+    zero, one = torch.zeros_like(xg), torch.ones_like(xg)
+    azr = torch.cat([xg, xg]).contiguous()
+    z, r, rh, q, out = (torch.empty_like(xg) for _ in range(5))
+    dev, st = _ffi.device_of(xg), _ffi.stream_of(xg)
+    p = lambda t: t.data_ptr()
+    _ffi.check(lib.dkt_gru_gate_zr_train(p(azr), p(zero), n, p(zero), n, p(one), n, p(z), p(r), p(rh), n, 1, 1, n, dev, st),
+               "dkt_gru_gate_zr_train")
+    _ffi.check(lib.dkt_gru_gate_out_train(p(xg), p(zero), n, p(one), p(one), n, p(q), p(out), n, 1, 1, n, dev, st),
+               "dkt_gru_gate_out_train")
+    torch.cuda.synchronize()
+    assert torch.equal(z, r)
+    xd = x.double()
+    res = {"points": n, "range": 30.0}
+    for name, got, true in (("sigmoid", z, 1.0 / (1.0 + torch.exp(-xd))), ("tanh", q, torch.tanh(xd))):
+        d = (got.double().cpu() - true).abs()
+        nz = true != 0
+        ulp = torch.exp2(torch.floor(torch.log2(true.abs()[nz])) - 23)
+        k = int((d[nz] / ulp).argmax())
+        res[name] = {"worst_ulp": round(float((d[nz] / ulp).max()), 3), "at_x": float(x[nz][k]),
+                     "worst_relative_u": round(float((d[nz] / (true.abs()[nz] * 2.0 ** -24)).max()), 3)}
+    print(json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--arms", default="a,b")
+    ap.add_argument("--no-raw", action="store_true")
+    ap.add_argument("--sweep", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_gru_train.py measures on a HIP device; none is available")
+    if a.sweep:
+        return sweep()
+    arms = a.arms.split(",")
+    blk = make_block()
+    net0, inp, corr, flow, wd, wm = make_inputs()
+    params = list(blk.parameters())
+
+    def step(arm):
+        BasicMultiUpdateBlock.TRAIN_NODES = arm == "b"
+        for t in params:
+            t.grad = None
+        net = [t.clone().requires_grad_(True) for t in net0]
+        loss = 0.0
+        for it in range(ITERS):
+            net, mask, delta = blk(net, inp, corr, flow)
+            loss = loss + (delta * wd[it]).sum() + (mask * wm[it]).sum()
+        loss.backward()
+
+    for _ in range(a.warmup):
+        for arm in arms:
+            step(arm)
+    torch.cuda.synchronize()
+    wall = {arm: [] for arm in arms}
+    peak = {}
+    for _ in range(a.steps):
+        for arm in arms:
+            for t in params:
+                t.grad = None                                   # the peak counts what one step allocates, gradients included
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            t0 = time.perf_counter()
+            step(arm)
+            torch.cuda.synchronize()
+            wall[arm].append((time.perf_counter() - t0) * 1e3)
+            peak[arm] = (torch.cuda.max_memory_allocated(), base)
+    BasicMultiUpdateBlock.TRAIN_NODES = True
+    out = {"B": B, "H": 4 * H, "W": 4 * W, "n_gru_layers": 3, "calls": ITERS, "steps": a.steps}
+    for arm in arms:
+        w = sorted(wall[arm])
+        out["arm_" + arm] = {"wall_ms_median": round(w[len(w) // 2], 3), "wall_ms_min": round(w[0], 3),
+                             "max_memory_allocated_MB": round(peak[arm][0] / 1e6, 1),
+                             "allocated_before_step_MB": round(peak[arm][1] / 1e6, 1)}
+    if "a" in arms and "b" in arms:
+        out["speedup_b_over_a"] = round(out["arm_a"]["wall_ms_median"] / out["arm_b"]["wall_ms_median"], 3)
+    if "b" in arms and not a.no_raw:
+        out["raw_calls"] = raw_calls()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
