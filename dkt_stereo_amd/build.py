@@ -49,12 +49,12 @@ def build(force=False, verbose=False):
         return LIB
     os.makedirs(OBJ_DIR, exist_ok=True)
     # one object per source, compiled in parallel; conv2d.hip (the long pole: dozens of kernel
-    # instantiations) is compiled as four translation units selected by -DCONV_TU_PASSES
+    # instantiations) is compiled as seven translation units selected by -DCONV_TU_PASSES
     jobs = []
     for src in sources():
         stem = os.path.splitext(os.path.basename(src))[0]
         if stem == "conv2d":
-            for tu in (0, 1, 2, 3):
+            for tu in (0, 1, 2, 3, 4, 5, 6):
                 jobs.append((src, os.path.join(OBJ_DIR, "conv2d_tu%d.o" % tu), ["-DCONV_TU_PASSES=%d" % tu]))
         else:
             jobs.append((src, os.path.join(OBJ_DIR, stem + ".o"), EXTRA_FLAGS.get(stem, [])))

@@ -125,15 +125,16 @@ class _Packed:
     __slots__ = ("key", "hi", "lo", "inv_scale", "bias")
 
 
-def _packed_weights(layer, src_channels):
+def _packed_weights(layer, src_channels, scale=None):
     """Split-fp16 weight image for dkt_conv2d_f16s, cached on the layer PER DEVICE (the shallow module
     copies of nn.parallel.replicate share the cache dict; their parameters live on different devices)
-    and rebuilt when the parameter tensor is replaced or written."""
+    and rebuilt when the parameter tensor is replaced or written.  `scale`: the power-of-two weight scale when
+    the caller already knows it (a rearrangement of a packed weight), else it is read from max|w| (a host sync)."""
     with _CACHE_LOCK:
-        return _packed_weights_locked(layer, src_channels)
+        return _packed_weights_locked(layer, src_channels, scale)
 
 
-def _packed_weights_locked(layer, src_channels):
+def _packed_weights_locked(layer, src_channels, scale=None):
     w = layer.weight
     b = layer.bias
     key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version), tuple(src_channels))
@@ -151,10 +152,11 @@ def _packed_weights_locked(layer, src_channels):
     elems = L.dkt_conv2d_packed_elems(ch, n, cout, kh, kw)
     if elems <= 0:
         raise _ffi.DktError("dkt_conv2d_packed_elems rejected the layer shape")
-    wmax = float(w.detach().abs().max())
-    # power-of-two scale putting max|w| in [2^12, 2^13): keeps w_lo out of the fp16 subnormals
-    e = 12 - math.floor(math.log2(wmax)) if wmax > 0 else 0
-    scale = 2.0 ** e
+    if scale is None:
+        wmax = float(w.detach().abs().max())
+        # power-of-two scale putting max|w| in [2^12, 2^13): keeps w_lo out of the fp16 subnormals
+        e = 12 - math.floor(math.log2(wmax)) if wmax > 0 else 0
+        scale = 2.0 ** e
     p = _Packed()
     p.hi = torch.empty(elems, device=w.device, dtype=torch.float16)
     p.lo = torch.empty(elems, device=w.device, dtype=torch.float16)
@@ -225,6 +227,7 @@ def clear_weight_cache(module):
             m.__dict__.pop("_dkt_stem7", None)
             m.__dict__.pop("_dkt_wt", None)
             m.__dict__.pop("_dkt_view", None)
+            m.__dict__.pop("_dkt_grad", None)
             if hasattr(m, "_zr_cache"):
                 m._zr_cache = None
 
@@ -393,7 +396,7 @@ def _stem7_packed(layer, key, L):
 class _Operands:
     """The cat operands of one convolution marshalled for the C ABI (keeps them alive)."""
 
-    def __init__(self, x, layer):
+    def __init__(self, x, layer, pack_scale=None):
         srcs = list(x) if isinstance(x, (list, tuple)) else [x]
         if len(srcs) > 4:
             srcs = srcs[:3] + [torch.cat(srcs[3:], dim=1)]
@@ -404,7 +407,7 @@ class _Operands:
         self.B, _, self.H, self.W = srcs[0].shape
         chans = [int(s.shape[1]) for s in srcs]
         self.n = n = len(srcs)
-        self.pk = _packed_weights(layer, chans)
+        self.pk = _packed_weights(layer, chans, pack_scale)
         self.ptrs = (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs])
         self.ch = (ctypes.c_int * n)(*chans)
         self.bs = (ctypes.c_long * n)(*[s.stride(0) for s in srcs])
@@ -670,7 +673,20 @@ def conv2d_gate_out(x, q_layer, cq, z, h, out=None):
 # same convolution with the weights transposed over (Cout, Cin) and rotated by 180 degrees), the weight gradient -- a
 # reduction over all pixels, a different loop nest -- on the vendor library (torch.nn.grad.conv2d_weight), the bias gradient
 # is a sum.
+#
+# Backward with GRAD_PREPASS (default): one streaming pre-pass (dkt_conv_grad_prepass) masks the upstream gradient with the
+# saved ReLU output, sums the bias gradient in a fixed order and leaves the RANGE of the masked gradient in device memory;
+# the input-gradient convolution (dkt_conv2d_f16s_dscale) takes its activation scale from there, so a gradient of any
+# magnitude -- 1e-6 from a mean-reduced loss, 1e+6 under a loss scale -- keeps the ~22 bits of the split instead of the
+# format's absolute 2^-25 floor, and a power-of-two multiple of the upstream gradient gives that multiple of gx and gb bit
+# for bit.  The host reads nothing back.  The packed images of both orientations live on a persistent OWNER (the nn.Module,
+# or ConvGRU._merged_zr() for z|r), keyed on the weight's (data_ptr, _version): packed once per optimizer step, not per call.
 # ---------------------------------------------------------------------------------------------------------------------
+#: backward of conv2d_autograd: True = pre-pass + device-scaled input gradient + owner-held packs; False = the sequence
+#: before them (the A/B handle of tools/bench_gru_train.py, in the style of BasicMultiUpdateBlock.TRAIN_NODES)
+GRAD_PREPASS = True
+
+
 class _LayerShim:
     """Duck-types the `layer` argument of conv2d() for detached tensors inside the autograd function."""
 
@@ -708,18 +724,153 @@ class _Conv2dFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
-def conv2d_autograd(x, layer, relu=False):
-    """[relu](conv(x) + bias) for a stride-1 "same" layer (odd square kernel, no groups / dilation) as an autograd node:
-    `x` a tensor or a list of tensors (the reference's torch.cat operands).  Other layers run as plain torch."""
-    if isinstance(x, (list, tuple)):
-        x = x[0] if len(x) == 1 else torch.cat(list(x), dim=1)
-    w = layer.weight
-    kh, kw = w.shape[2:]
+def _grad_layer(owner):
+    """The layer of the input gradient -- `owner`'s weight transposed over (Cout, Cin) and rotated by 180 degrees -- as a
+    persistent object on `owner`, per device, keyed on the weight's (data_ptr, _version); its own packed image hangs off it
+    (_packed_weights) and takes the scale of the forward image (the same max|w|: no host read)."""
+    w = owner.weight
+    key = (w.data_ptr(), w._version)
+    with _CACHE_LOCK:
+        cache = owner.__dict__.setdefault("_dkt_grad", {})
+        hit = cache.get(str(w.device))
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        kh, kw = w.shape[2:]
+        with torch.no_grad():
+            shim = _LayerShim(w.detach().float().transpose(0, 1).flip(2, 3).contiguous(), None, (kh // 2, kw // 2))
+        shim.pack_scale = None
+        for p in owner.__dict__.get("_dkt_packed", {}).values():
+            if p.key[:2] == key:
+                shim.pack_scale = 1.0 / p.inv_scale
+        cache[str(w.device)] = (key, shim)
+        return shim
+
+
+def _dscale_eligible(shim):
+    """The input gradient runs on dkt_conv2d_f16s_dscale: what conv2d() would send to dkt_conv2d_f16s."""
+    return hip_eligible(shim) and not few_eligible(shim) and not direct_eligible(shim)
+
+
+def _batch_stride(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2] * t.shape[3]
+
+
+def conv_grad_prepass(gy, y=None, want_bias=True):
+    """dkt_conv_grad_prepass on a dense-per-batch fp32 gradient: returns (g', gb, scale) -- g' = gy masked by y > 0 (gy
+    itself without y), gb the per-channel sum of g' (None unless wanted), scale the device pair {2^e, 2^-e} of max|g'|."""
+    _ffi.require_gpu(gy, *([] if y is None else [y]))
+    B, C, H, W = gy.shape
+    if not _dense(gy) or (B > 1 and gy.stride(0) < C * H * W):
+        gy = gy.contiguous()
+    if y is not None and (not _dense(y) or (B > 1 and y.stride(0) < C * H * W)):
+        y = y.contiguous()
+    L = _ffi.lib()
+    gm = None if y is None else torch.empty((B, C, H, W), device=gy.device, dtype=torch.float32)
+    gb = torch.empty(C, device=gy.device, dtype=torch.float32) if want_bias else None
+    scale = torch.empty(2, device=gy.device, dtype=torch.float32)
+    ws = torch.empty(int(L.dkt_conv_grad_prepass_ws_floats(B, C, H * W)), device=gy.device, dtype=torch.float32)
+    rc = L.dkt_conv_grad_prepass(gy.data_ptr(), _batch_stride(gy), None if y is None else y.data_ptr(),
+                                 0 if y is None else _batch_stride(y), None if gm is None else gm.data_ptr(),
+                                 None if gb is None else gb.data_ptr(), scale.data_ptr(), ws.data_ptr(), B, C, H * W,
+                                 _ffi.device_of(gy), _ffi.stream_of(gy))
+    _ffi.check(rc, "dkt_conv_grad_prepass")
+    return (gy if gm is None else gm), gb, scale
+
+
+def conv2d_dscale(g, layer, scale, pack_scale=None):
+    """Stride-1 convolution of `g` with `layer`'s weight (no bias) whose activation scale is the device pair `scale`
+    (dkt_conv2d_f16s_dscale): in_scale = scale[0], the result is un-scaled by scale[1] in the epilogue."""
+    op = _Operands(g, layer, pack_scale)
+    out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
+    rc = _ffi.lib().dkt_conv2d_f16s_dscale(op.ptrs, op.ch, op.bs, op.n, op.pk.hi.data_ptr(), op.pk.lo.data_ptr(),
+                                           op.pk.inv_scale, scale.data_ptr(), out.data_ptr(), out.stride(0), op.B, op.H,
+                                           op.W, op.cout, op.kh, op.kw, op.passes, _ffi.device_of(out), _ffi.stream_of(out))
+    _ffi.check(rc, "dkt_conv2d_f16s_dscale")
+    return out
+
+
+class _Conv2dGradFn(torch.autograd.Function):
+    """conv2d_autograd with GRAD_PREPASS.  apply(x, relu, owner, nparts, *params): `owner` holds the (detached) weight and
+    bias the kernels read and every packed image; `params` are the tensors autograd differentiates -- nparts weights, then
+    nparts biases or none -- whose concatenations along the output channels are owner.weight / owner.bias."""
+
+    @staticmethod
+    def forward(ctx, x, relu, owner, nparts, *params):
+        with torch.no_grad():
+            y = conv2d(x.detach(), owner, relu=relu)
+        ctx.owner, ctx.relu, ctx.nparts, ctx.has_bias = owner, bool(relu), nparts, len(params) > nparts
+        ctx.splits = [int(p.shape[0]) for p in params[:nparts]]
+        ctx.save_for_backward(x, owner.weight, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w, y = ctx.saved_tensors
+        n = ctx.nparts
+        need_x = ctx.needs_input_grad[0]
+        need_w = any(ctx.needs_input_grad[4:4 + n])
+        need_b = ctx.has_bias and any(ctx.needs_input_grad[4 + n:])
+        kh, kw = w.shape[2:]
+        gx = gw = gb = None
+        with torch.no_grad():
+            gy = gy if gy.dtype == torch.float32 else gy.float()
+            shim = _grad_layer(ctx.owner) if need_x else None
+            dscale = need_x and _dscale_eligible(shim)
+            g, scale = gy, None
+            if ctx.relu or need_b or dscale:
+                g, gb, scale = conv_grad_prepass(gy, y if ctx.relu else None, want_bias=need_b)
+            if need_x:
+                gx = conv2d_dscale(g, shim, scale, shim.pack_scale) if dscale else conv2d(g, shim)
+            if need_w:
+                gw = torch.nn.grad.conv2d_weight(x.detach(), w.shape, g, stride=1, padding=(kh // 2, kw // 2))
+        gws = [None] * n if gw is None else list(gw.split(ctx.splits, 0)) if n > 1 else [gw]
+        gbs = [None] * n if gb is None else list(gb.split(ctx.splits, 0)) if n > 1 else [gb]
+        gws = [t if ctx.needs_input_grad[4 + i] else None for i, t in enumerate(gws)]
+        gbs = [t if ctx.needs_input_grad[4 + n + i] else None for i, t in enumerate(gbs)] if ctx.has_bias else []
+        return (gx, None, None, None, *gws, *gbs)
+
+
+def _autograd_eligible(x, layer):
+    """fp32 HIP tensor, stride-1 "same" layer with an odd square kernel, no groups / dilation."""
+    kh, kw = layer.weight.shape[2:]
     pad = layer.padding
     pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
-    if (not x.is_cuda or x.dtype != torch.float32 or kh != kw or kh % 2 == 0 or pad != (kh // 2, kw // 2)
-            or _stride_of(layer) != (1, 1) or not _plain_conv(layer)):
+    return (x.is_cuda and x.dtype == torch.float32 and kh == kw and kh % 2 == 1 and pad == (kh // 2, kw // 2)
+            and _stride_of(layer) == (1, 1) and _plain_conv(layer))
+
+
+def conv2d_autograd(x, layer, relu=False, owner=None):
+    """[relu](conv(x) + bias) for a stride-1 "same" layer (odd square kernel, no groups / dilation) as an autograd node:
+    `x` a tensor or a list of tensors (the reference's torch.cat operands).  Other layers run as plain torch.
+    `layer` may be a tuple of layers that share input and geometry (ConvGRU's convz, convr): their outputs are
+    concatenated along channels, one convolution, and `owner` is then required.
+    `owner`: a PERSISTENT Conv2d-like object whose weight / bias hold the values of `layer`'s (of the concatenation, for a
+    tuple) and on which the packed images of the forward and of the input gradient are cached, keyed on the version of
+    its weight; default `layer` itself when it is an nn.Module.  Without either the images are packed per call."""
+    if isinstance(x, (list, tuple)):
+        x = x[0] if len(x) == 1 else torch.cat(list(x), dim=1)
+    if isinstance(layer, (list, tuple)):
+        parts = list(layer)
+        if owner is None:
+            raise ValueError("conv2d_autograd: a tuple of layers needs the owner that holds their concatenation")
+        if GRAD_PREPASS and _autograd_eligible(x, owner):
+            params = [p.weight for p in parts] + ([] if parts[0].bias is None else [p.bias for p in parts])
+            return _Conv2dGradFn.apply(x.contiguous(), relu, owner, len(parts), *params)
+        merged = _LayerShim(torch.cat([p.weight for p in parts], 0),
+                            None if parts[0].bias is None else torch.cat([p.bias for p in parts], 0), parts[0].padding)
+        return conv2d_autograd(x, merged, relu=relu)
+    w = layer.weight
+    if not _autograd_eligible(x, layer):
         y = F.conv2d(x, w, layer.bias, stride=_stride_of(layer), padding=layer.padding,
                      dilation=getattr(layer, "dilation", 1), groups=getattr(layer, "groups", 1))
         return F.relu(y) if relu else y
+    kh, kw = w.shape[2:]
+    pad = (kh // 2, kw // 2)
+    if GRAD_PREPASS:
+        if owner is None:
+            # a persistent module owns its images; anything else (a namespace around temporaries) packs per call, on an
+            # object that dies with the call
+            owner = layer if isinstance(layer, torch.nn.Module) else _LayerShim(
+                w.detach(), None if layer.bias is None else layer.bias.detach(), pad)
+        return _Conv2dGradFn.apply(x.contiguous(), relu, owner, 1, *([w] if layer.bias is None else [w, layer.bias]))
     return _Conv2dFn.apply(x.contiguous(), w, layer.bias, relu)

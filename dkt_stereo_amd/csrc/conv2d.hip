@@ -93,6 +93,9 @@ struct ConvArgs {
     //      out = relu(e_c0 + [relu](v))
     // Instance-norm of the INPUT folded into the staging (kernel instantiations with NRM = 1; one source):
     // (mean, 1/std) per (batch, channel) plane; the kernel convolves relu((x - mean) * invstd).
+    // Kernel instantiations with DSC = 1 (never together with NRM) find the device-resident scales in this slot instead, so
+    // that the argument block keeps its layout: in_norm[0] replaces in_scale, out_scale is multiplied by in_norm[1] -- the
+    // pair dkt_conv_grad_prepass writes, read by the kernel, never by the host.
     const float *in_norm;
     // Instance-norm statistics of the OUTPUT accumulated in the epilogue (epi 0): every wave writes the sums and sums of
     // squares of its channels over its rows x 32 columns to stats_ws[((b * entries + e) * Cout + co) * 2 + {0, 1}], entry
@@ -136,8 +139,13 @@ struct ConvArgsPair {
     ConvArgs p[2];
 };
 
-template <int KS, int WM, int WN, int NF, int PASSES, int MF = 2, int ST = 1, int CK = 2, int NRM = 0>
+// DSC = 1: in_scale / out_scale come from device memory -- the input gradient of a convolution, whose
+// range only the device knows (conv_grad.hip; the pair sits in ConvArgs::in_norm).  Instantiated for the tile shapes of the stride-1 selection alone, in
+// translation units of their own; with DSC = 0 the flag compiles to nothing (the code of every other instantiation is the
+// code it had without the flag).
+template <int KS, int WM, int WN, int NF, int PASSES, int MF = 2, int ST = 1, int CK = 2, int NRM = 0, int DSC = 0>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) void conv2d_f16s_kernel(ConvArgsPair ap, int nb0) {
+    static_assert(!(DSC && (NRM || ST != 1)), "the device scales share the argument slot of in_norm; stride 1 only");
     // Two independent convolutions may share one launch (dkt_conv2d_f16s_pair): blocks [0, nb0) stream
     // the tiles of problem 0, the others those of problem 1 -- a small layer (the coarsest GRU: 36
     // tiles) then rides in the tile-quantisation slack of a large one (the finest GRU: 460 tiles on
@@ -147,6 +155,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
     const ConvArgs &a = ap.p[second ? 1 : 0];      // uniform index into the kernel-argument segment: scalar loads
     const int blk_first = second ? nb0 : 0;
     const int blk_count = second ? (int)gridDim.x - nb0 : nb0;
+    // DSC: the scales come from device memory (wave-uniform: pinned into SGPRs); both factors are powers of two
+    const float dsc_in = DSC ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.in_norm[0]))) : 0.0f;
+    const float dsc_out = DSC ? __fmul_rn(a.out_scale, __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(a.in_norm[1])))) : 0.0f;
     constexpr int HALO = KS / 2;
     constexpr int TR = NF * WN;              // output rows per block
     // ST = 2: stride-2 convolution (the encoders' down-sampling layers).  Tiles are OUTPUT tiles;
@@ -275,8 +286,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
             const float v1 = (2 * q + 1 < snch && sok[it]) ? u1 : 0.0f;
             // range: |x * in_scale| must stay below 65520 (the fp16 hi part); beyond that -- and for
             // NaN / Inf inputs -- the result is non-finite, never a silently saturated value
-            const float x0 = v0 * a.in_scale;
-            const float x1 = v1 * a.in_scale;
+            const float x0 = v0 * (DSC ? dsc_in : a.in_scale);
+            const float x1 = v1 * (DSC ? dsc_in : a.in_scale);
             const _Float16 h0_ = (_Float16)x0, h1_ = (_Float16)x1;
             shw[it][q] = pack_h2(h0_, h1_);
             if (NPLANES == 2) slw[it][q] = pack_h2((_Float16)(x0 - (float)h0_), (_Float16)(x1 - (float)h1_));
@@ -398,7 +409,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int dco = m * 32 + (r & 3) + 8 * (r >> 2);
-                        float v = acc[m][n][r] * a.out_scale + bv[m][r];
+                        float v = acc[m][n][r] * (DSC ? dsc_out : a.out_scale) + bv[m][r];
                         if (a.relu) v = dkt_relu(v);
                         if (all_co || co_lane + dco < a.Cout) op[dco * oHW] = v;
                     }
@@ -420,7 +431,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
                         for (int mm = 0; mm < nm; ++mm)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
-                                float v = acc[m0 + mm][n][r] * a.out_scale + bv[m0 + mm][r];
+                                float v = acc[m0 + mm][n][r] * (DSC ? dsc_out : a.out_scale) + bv[m0 + mm][r];
                                 if (a.relu) v = dkt_relu(v);
                                 v = ok ? v : 0.0f;
                                 s1[mm * 16 + r] = __fadd_rn(s1[mm * 16 + r], v);
@@ -498,7 +509,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
                     const int dco = m * 32 + (r & 3) + 8 * (r >> 2);
                     if (!(all_co || co_lane + dco < a.Cout)) continue;
                     const long o = (long)dco * iHW + px;
-                    const float v = acc[m][n][r] * a.out_scale + bv[m][r];
+                    const float v = acc[m][n][r] * (DSC ? dsc_out : a.out_scale) + bv[m][r];
                     if (a.epi == 1) {
                         const float g = conv_sigmoid(__fadd_rn(v, gc[i]));
                         po[o] = second ? __fmul_rn(g, gh[i]) : g;
@@ -673,12 +684,12 @@ struct ConvSecond {
     int B;
 };
 
-template <int KS, int WM, int WN, int NF, int PASSES, int MF = 2, int ST = 1, int CK = 2, int NRM = 0>
+template <int KS, int WM, int WN, int NF, int PASSES, int MF = 2, int ST = 1, int CK = 2, int NRM = 0, int DSC = 0>
 static int launch_conv(ConvArgs a, int B, hipStream_t st, const ConvSecond *sec = nullptr) {
     constexpr int NPP = ((NF * WN - 1) * ST + KS) * (31 * ST + KS);
     constexpr int STAGE = NPP * (8 * CK + 4) * (PASSES == 3 ? 2 : 1);
     const size_t lds = ((size_t)2 * STAGE + 8) * sizeof(unsigned);   // + dummy words for surplus staging lanes
-    auto kern = conv2d_f16s_kernel<KS, WM, WN, NF, PASSES, MF, ST, CK, NRM>;
+    auto kern = conv2d_f16s_kernel<KS, WM, WN, NF, PASSES, MF, ST, CK, NRM, DSC>;
     // once per device and instantiation (and never inside a stream capture after warm-up)
     static int slots[64] = {0};                        // benign race: worst case computed twice
     int dev = 0;
@@ -830,9 +841,43 @@ static int launch_conv_stride2(const ConvArgs &a, int B, hipStream_t st) {
     return launch_conv<KS, 4, 1, 1, PASSES, 2, 2>(a, B, st);                      // 256 co x 1 row
 }
 
+// The stride-1 selection of launch_conv_shape for the device-scaled kernel (dkt_conv2d_f16s_dscale: one problem, epilogue 0,
+// no input norm): the same thresholds, the same tile shapes -- a convolution and the input gradient of a layer of its size
+// run the same loop nest.  (The 64 -> 64 layers take the generic 64-channel tile, not conv_ws.h's weights-stationary kernel.)
+template <int KS, int PASSES>
+static int launch_conv_shape_dscale(const ConvArgs &a, int B, hipStream_t st) {
+    const long tiles4 = (long)a.tiles_w * ((a.H + 3) / 4) * B;
+    const long few = CONV_FEW_TILES;
+    if (a.Cout <= 32) return launch_conv<KS, 1, 4, 1, PASSES, 1, 1, 2, 0, 1>(a, B, st);
+    if (a.Cout <= 64) {
+        if constexpr (KS == 3) {
+            if (tiles4 / 2 >= 512) return launch_conv<KS, 1, 4, 2, PASSES, 2, 1, 1, 0, 1>(a, B, st);
+        }
+        return launch_conv<KS, 1, 4, 1, PASSES, 2, 1, 2, 0, 1>(a, B, st);
+    }
+    if (a.Cout <= 128) {
+        if constexpr (KS == 3) {
+            if (a.Cout <= 96 && tiles4 >= few) return launch_conv<KS, 1, 4, 1, PASSES, 3, 1, 2, 0, 1>(a, B, st);
+        }
+        if (tiles4 < few) return launch_conv<KS, 2, 2, 1, PASSES, 2, 1, 2, 0, 1>(a, B, st);
+        return launch_conv<KS, 2, 2, 2, PASSES, 2, 1, 2, 0, 1>(a, B, st);
+    }
+    if constexpr (KS == 3) {
+        if (a.Cout > 256 && a.Cout <= 384 && (long)a.tiles_w * ((a.H + 1) / 2) * B >= 512)
+            return launch_conv<KS, 4, 1, 2, PASSES, 3, 1, 2, 0, 1>(a, B, st);
+    }
+    const long tiles2 = (long)a.tiles_w * ((a.H + 1) / 2) * B * ((a.Cout + 255) / 256);
+    if (tiles2 < few) return launch_conv<KS, 4, 1, 1, PASSES, 2, 1, 2, 0, 1>(a, B, st);
+    if (tiles4 * ((a.Cout + 255) / 256) >= 256) {
+        if constexpr (KS == 3) return launch_conv<KS, 4, 2, 2, PASSES, 2, 1, 2, 0, 1>(a, B, st);
+    }
+    return launch_conv<KS, 4, 1, 2, PASSES, 2, 1, 2, 0, 1>(a, B, st);
+}
+
 // The kernel instantiations are split by number of MFMA passes so that the build can compile them as
-// three parallel translation units (dkt_stereo_amd/build.py: -DCONV_TU_PASSES=1|2|3; =0 holds the ABI
-// and the weight packer).  Compiled without the macro this file is one complete translation unit.
+// parallel translation units (dkt_stereo_amd/build.py: -DCONV_TU_PASSES=1|2|3, =4|5|6 the device-scaled
+// instantiations of 1|2|3 passes; =0 holds the ABI and the weight packer).  Compiled without the macro this
+// file is one complete translation unit.
 int conv2d_launch_p1(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec);
 int conv2d_launch_p2(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec);
 int conv2d_launch_p3(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec);
@@ -863,6 +908,24 @@ int conv2d_launch_p2(const ConvArgs &a, int B, int KH, int stride, hipStream_t s
 #endif
 #if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 3
 int conv2d_launch_p3(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec) { return conv2d_launch_passes<3>(a, B, KH, stride, st, sec); }
+#endif
+
+int conv2d_launch_dscale_p1(const ConvArgs &a, int B, int KH, hipStream_t st);
+int conv2d_launch_dscale_p2(const ConvArgs &a, int B, int KH, hipStream_t st);
+int conv2d_launch_dscale_p3(const ConvArgs &a, int B, int KH, hipStream_t st);
+template <int PASSES>
+static int conv2d_launch_dscale(const ConvArgs &a, int B, int KH, hipStream_t st) {
+    if (KH == 3) return launch_conv_shape_dscale<3, PASSES>(a, B, st);
+    return launch_conv_shape_dscale<1, PASSES>(a, B, st);
+}
+#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 4
+int conv2d_launch_dscale_p1(const ConvArgs &a, int B, int KH, hipStream_t st) { return conv2d_launch_dscale<1>(a, B, KH, st); }
+#endif
+#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 5
+int conv2d_launch_dscale_p2(const ConvArgs &a, int B, int KH, hipStream_t st) { return conv2d_launch_dscale<2>(a, B, KH, st); }
+#endif
+#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 6
+int conv2d_launch_dscale_p3(const ConvArgs &a, int B, int KH, hipStream_t st) { return conv2d_launch_dscale<3>(a, B, KH, st); }
 #endif
 
 #if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 0
@@ -1021,6 +1084,22 @@ extern "C" int dkt_conv2d_f16s(const float *const *src, const int *src_channels,
                                int device, void *stream) {
     return conv2d_f16s_impl(src, src_channels, src_bstride, nsrc, w_hi, w_lo, bias, out_scale, in_scale, out, out_bstride,
                             B, H, W, Cout, KH, KW, relu, passes, nullptr, device, stream);
+}
+
+extern "C" int dkt_conv2d_f16s_dscale(const float *const *src, const int *src_channels, const long *src_bstride,
+                                      int nsrc, const void *w_hi, const void *w_lo, float w_inv_scale, const float *scale,
+                                      float *out, long out_bstride, int B, int H, int W, int Cout, int KH, int KW,
+                                      int passes, int device, void *stream) {
+    if (!scale) return DKT_E_NULL;
+    ConvArgs a;
+    const int rc = conv_fill(a, src, src_channels, src_bstride, nsrc, w_hi, w_lo, nullptr, w_inv_scale, 1.0f, out,
+                             out_bstride, B, H, W, Cout, KH, KW, 0, passes, nullptr, 1);
+    if (rc != DKT_OK) return rc;
+    a.in_norm = scale;         // DSC: in_scale = scale[0], out_scale = w_inv_scale * scale[1], both read by the kernel
+    DKT_ENTER(device);
+    if (passes == 3) return conv2d_launch_dscale_p3(a, B, KH, (hipStream_t)stream);
+    if (passes == 2) return conv2d_launch_dscale_p2(a, B, KH, (hipStream_t)stream);
+    return conv2d_launch_dscale_p1(a, B, KH, (hipStream_t)stream);
 }
 
 extern "C" int dkt_conv2d_f16s_strided(const float *const *src, const int *src_channels, const long *src_bstride,

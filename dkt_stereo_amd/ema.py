@@ -54,8 +54,9 @@ PACK_HOOKS = {
     "_dkt_packed_c8": _conv_c8._refresh_packed_c8,
     "_dkt_gru_c8": _conv_c8._refresh_gru_c8,
 }
-#: per-layer caches that hold no weight derivative
-NOT_WEIGHTS = {"_dkt_c8_buf"}
+#: per-layer caches that hold no weight derivative, or one that no captured launch reads and that is keyed on the weight's
+#: version, i.e. rebuilt by its next use (the input-gradient images of conv.conv2d_autograd's backward)
+NOT_WEIGHTS = {"_dkt_c8_buf", "_dkt_grad"}
 
 
 class _Refresh:

@@ -33,6 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _ffi, gru_train
+from . import conv as _conv
 from .conv import (_CACHE_LOCK, conv2d, conv2d_accumulate, conv2d_gate_out, conv2d_gate_out_pair, conv2d_gate_zr,
                    conv2d_autograd, conv2d_gate_zr_pair, conv2d_pair, few_eligible, get_backend, hip_eligible, pair_eligible)
 
@@ -624,9 +625,13 @@ class BasicMultiUpdateBlock(nn.Module):
     def _gru_autograd(cls, gru, h, cz, cr, cq, *xs):
         """core/update.py:23-32 on differentiable convolutions (conv.conv2d_autograd); z and r share one convolution."""
         hx = torch.cat([h, *xs], dim=1)
-        zr = SimpleNamespace(weight=torch.cat([gru.convz.weight, gru.convr.weight], 0),
-                             bias=torch.cat([gru.convz.bias, gru.convr.bias], 0), padding=gru.convz.padding)
-        a = conv2d_autograd(hx, zr)
+        if _conv.GRAD_PREPASS and hx.is_cuda and hx.dtype == torch.float32:
+            # the merged z|r layer is cached per device and keyed on the four parameters' versions: it owns the packed images
+            a = conv2d_autograd(hx, (gru.convz, gru.convr), owner=gru._merged_zr())
+        else:
+            zr = SimpleNamespace(weight=torch.cat([gru.convz.weight, gru.convr.weight], 0),
+                                 bias=torch.cat([gru.convz.bias, gru.convr.bias], 0), padding=gru.convz.padding)
+            a = conv2d_autograd(hx, zr)
         if cls._train_nodes(a, h, cz, cr, cq, *xs):
             z, rh = gru_train.gate_zr(a, cz, cr, h)
             return gru_train.gate_out(conv2d_autograd(torch.cat([rh, *xs], dim=1), gru.convq), cq, z, h)

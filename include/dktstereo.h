@@ -364,6 +364,41 @@ int dkt_conv2d_f16s(const float *const *src, const int *src_channels, const long
                     float *out, long out_bstride, int B, int H, int W, int Cout, int KH, int KW,
                     int relu, int passes, int device, void *stream);
 
+/* ---- backward of the update-operator convolutions (training; dkt_stereo_amd/conv.py: _Conv2dFn.backward) ----
+ * torch autograd through [relu](conv2d(x, w, b)), stride 1, "same" padding (core/update.py:9-10, 19-21, 72-76, 111-113):
+ *   g' = gy * (y > 0),  gb = g'.sum((0, 2, 3)),  gx = conv2d(g', w transposed over (Cout, Cin) and rotated by 180 degrees).
+ *
+ * dkt_conv_grad_prepass: one streaming pass over gy (B, C, HW; batch stride gy_bstride, each batch element dense) and a
+ * one-block finish; the host reads nothing back.
+ *   y      (optional) the saved output of a ReLU layer, batch stride y_bstride.  With y:  gmask[b,c,i] = y > 0 ? gy : 0,
+ *          dense (B, C, HW), required.  Without y nothing is copied (g' is gy itself) and gmask is ignored.
+ *   gb     (optional) C floats: the sum of g' over (b, i) in an order fixed by the shape alone -- a plane in segments of
+ *          4096 elements, one segment per block; no float atomics -- bit-identical from run to run, for every grid size and
+ *          for the 16-byte and the 4-byte path alike.
+ *   scale  two floats {2^e, 2^-e}: e = 12 - floor(log2(max|g'|)), i.e. max|g'| * 2^e in [2^12, 2^13) (the window
+ *          dkt_conv2d_pack_weights' callers put the weights in), clamped to |e| <= DKT_CONV_GRAD_MAX_EXP, which keeps both
+ *          floats, and out_scale of dkt_conv2d_f16s_dscale for any weight scale in [2^-46, 2^46], normal; e = 0 when
+ *          max|g'| is 0, Inf or NaN (a non-finite gradient is passed on as it is and comes out non-finite).
+ *   ws     dkt_conv_grad_prepass_ws_floats(B, C, HW) floats of scratch, written before they are read.
+ * 16-byte accesses when HW, the batch strides and the pointers allow it, 4-byte ones otherwise.
+ * Errors: gy, scale or ws null, or y without gmask, DKT_E_NULL; B, C, HW <= 0 or a batch stride shorter than C*HW
+ * DKT_E_SHAPE. */
+#define DKT_CONV_GRAD_MAX_EXP 80
+long dkt_conv_grad_prepass_ws_floats(int B, int C, long HW);
+int dkt_conv_grad_prepass(const float *gy, long gy_bstride, const float *y, long y_bstride,
+                          float *gmask, float *gb, float *scale, float *ws,
+                          int B, int C, long HW, int device, void *stream);
+
+/* dkt_conv2d_f16s (stride 1, no bias, no ReLU, no epilogue) with the activation scale in DEVICE memory: the input-gradient
+ * convolution, whose operand range only the device knows.  scale = {s, 1/s} as dkt_conv_grad_prepass writes it:
+ *   in_scale = scale[0],  out_scale = w_inv_scale * scale[1]   (w_inv_scale: 1 / the weight scale of the pack),
+ * read by the kernel; a gradient of any magnitude keeps the ~22 bits of the split, and a power-of-two multiple of the
+ * operand gives that multiple of the result bit for bit.  Errors as dkt_conv2d_f16s, scale null DKT_E_NULL. */
+int dkt_conv2d_f16s_dscale(const float *const *src, const int *src_channels, const long *src_bstride, int nsrc,
+                           const void *w_hi, const void *w_lo, float w_inv_scale, const float *scale,
+                           float *out, long out_bstride, int B, int H, int W, int Cout, int KH, int KW,
+                           int passes, int device, void *stream);
+
 /* dkt_conv2d_f16s with a stride (1 or 2) and padding K/2: the down-sampling convolutions of the
  * encoders (core/extractor.py:16,34: 3x3 stride 2 and the 1x1 stride-2 projection).  H, W are the
  * INPUT size; out is (B, Cout, (H-1)/stride+1, (W-1)/stride+1). */

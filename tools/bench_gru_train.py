@@ -7,16 +7,24 @@ updates and masks; the weights are trainable (their gradient is the vendor libra
   arm a  BasicMultiUpdateBlock.TRAIN_NODES = False: gates and resamplers as torch's expression sequence (training before
          the nodes);
   arm b  TRAIN_NODES = True: gru_train.gate_zr / gate_out / pool2x / interp (dkt_gru_gate_*_train, dkt_gru_gate_*_bwd,
-         dkt_pool2x_bwd, dkt_interp_bilinear_bwd).
+         dkt_pool2x_bwd, dkt_interp_bilinear_bwd), the convolutions' backward as before conv.GRAD_PREPASS;
+  arm c  arm b with conv.GRAD_PREPASS = True: dkt_conv_grad_prepass + dkt_conv2d_f16s_dscale, packed images held by their
+         owners (the default; on a tree without the handle arm b is that tree's only backward).
 
 The arms alternate in one process after warm-up.  Per arm: wall ms of a step (host clock around a step that ends in a
-synchronise; median and minimum) and torch.cuda.max_memory_allocated over a step.  "raw_calls": every new entry at the
+synchronise; median and minimum), torch.cuda.max_memory_allocated over a step, the library launches of a step's FORWARD by
+entry (_ffi.launch_log is per thread; the backward runs on autograd's thread and shows in the rocprofv3 run) and the host
+synchronisations torch reports for one more step (torch.cuda.set_sync_debug_mode("warn")).  "raw_calls": every new entry at the
 finest level's shape issued back to back through the C ABI on one stream, buffer sets in rotation (past the 256 MiB
 Infinity Cache), HIP events around the calls, median of 5: us per call and the fraction of 8 TB/s its compulsory bytes
 would take.  Launch counts and kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of `--arms a` /
 `--arms b`.
 
     python tools/bench_gru_train.py [--steps 10] [--warmup 3] [--arms a,b] [--no-raw]
+    python tools/bench_gru_train.py --prepass   dkt_conv_grad_prepass alone at (2, 256, 120, 224), with and without y,
+                                                against its compulsory bytes
+    python tools/bench_gru_train.py --gx-table  relative error of the input gradient of the z|r layer (1, 256 -> 384, 16 x 24)
+                                                against float64 at upstream gradients randn * 2^k, both backward paths
     python tools/bench_gru_train.py --sweep     worst error of the device's sigmoid (dkt_sigmoid) and tanhf against float64
                                                 on linspace(-30, 30, 4 000 001): the E_sigma / E_t of tests/_gru_ref.py
 """
@@ -25,6 +33,7 @@ import json
 import os
 import sys
 import time
+import warnings
 from types import SimpleNamespace
 
 import torch
@@ -32,7 +41,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from dkt_stereo_amd import _ffi  # noqa: E402
+from dkt_stereo_amd import _ffi, conv  # noqa: E402
 from dkt_stereo_amd.update import BasicMultiUpdateBlock  # noqa: E402
 
 PEAK_BPS = 8e12
@@ -114,6 +123,66 @@ def raw_calls(sets=4, rounds=6, reps=5):
     return out
 
 
+def prepass_alone(sets=6, rounds=4, reps=5):
+    """dkt_conv_grad_prepass at the z|r gradient of the recipe shape, buffer sets in rotation past the Infinity Cache."""
+    lib = _ffi.lib()
+    C, HW = 2 * CH, H * W
+    n = C * HW
+    bufs = [dict(gy=torch.randn(B, C, H, W, device="cuda"), y=torch.randn(B, C, H, W, device="cuda"),
+                 gm=torch.empty(B, C, H, W, device="cuda")) for _ in range(sets)]
+    gb, scale = torch.empty(C, device="cuda"), torch.empty(2, device="cuda")
+    ws = torch.empty(int(lib.dkt_conv_grad_prepass_ws_floats(B, C, HW)), device="cuda")
+    dev, st = _ffi.device_of(gb), _ffi.stream_of(gb)
+    p = lambda t: t.data_ptr()
+    out = {"shape": [B, C, H, W]}
+    for name, with_y, planes in (("without_y", False, 1), ("with_y", True, 3)):
+        fn = lambda t: lib.dkt_conv_grad_prepass(p(t["gy"]), n, p(t["y"]) if with_y else None, n, p(t["gm"]), p(gb), p(scale),
+                                                 p(ws), B, C, HW, dev, st)
+        for t in bufs:
+            _ffi.check(fn(t), "dkt_conv_grad_prepass")
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(rounds):
+                for t in bufs:
+                    fn(t)
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3 / (rounds * len(bufs)))
+        med = sorted(us)[len(us) // 2]
+        nbytes = planes * B * n * 4
+        out[name] = {"us_per_call": round(med, 2), "compulsory_MB": round(nbytes / 1e6, 2),
+                     "frac_of_8TBps": round(nbytes / PEAK_BPS / (med * 1e-6), 3)}
+    print(json.dumps(out))
+
+
+def gx_table():
+    """max|gx - exact| / max|exact| of the z|r layer's input gradient, exact = float64 on the device."""
+    import torch.nn.functional as F
+    torch.manual_seed(0)
+    lay = torch.nn.Conv2d(3 * CH, 2 * CH, 3, padding=1).cuda()
+    x0 = torch.randn(1, 3 * CH, 16, 24, device="cuda")
+    gy0 = torch.randn(1, 2 * CH, 16, 24, device="cuda")
+    wt = lay.weight.detach().transpose(0, 1).flip(2, 3).double()
+    out = {}
+    for k in (0, -10, -20, -30):
+        gy = gy0 * 2.0 ** k
+        exact = F.conv2d(gy.double(), wt, padding=1)
+        row = {}
+        for name, on in (("before", False), ("prepass", True)):
+            if not hasattr(conv, "GRAD_PREPASS") and on:
+                continue
+            conv.GRAD_PREPASS = on
+            x = x0.clone().requires_grad_(True)
+            gx = torch.autograd.grad(conv.conv2d_autograd(x, lay), [x], grad_outputs=gy)[0]
+            row[name] = float("%.3g" % float((gx.double() - exact).abs().max() / exact.abs().max()))
+        out["k=%d" % k] = row
+    conv.GRAD_PREPASS = True
+    print(json.dumps(out))
+
+
 def sweep():
     """Worst error of dkt_sigmoid and tanhf (through the training entries: x + 0 is exact) in ulp of the true result and
     relative to it in u = 2^-24."""
@@ -151,18 +220,25 @@ def main():
     ap.add_argument("--arms", default="a,b")
     ap.add_argument("--no-raw", action="store_true")
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--prepass", action="store_true")
+    ap.add_argument("--gx-table", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_gru_train.py measures on a HIP device; none is available")
     if a.sweep:
         return sweep()
+    if a.prepass:
+        return prepass_alone()
+    if a.gx_table:
+        return gx_table()
     arms = a.arms.split(",")
     blk = make_block()
     net0, inp, corr, flow, wd, wm = make_inputs()
     params = list(blk.parameters())
 
     def step(arm):
-        BasicMultiUpdateBlock.TRAIN_NODES = arm == "b"
+        BasicMultiUpdateBlock.TRAIN_NODES = arm != "a"
+        conv.GRAD_PREPASS = arm == "c"
         for t in params:
             t.grad = None
         net = [t.clone().requires_grad_(True) for t in net0]
@@ -190,15 +266,33 @@ def main():
             torch.cuda.synchronize()
             wall[arm].append((time.perf_counter() - t0) * 1e3)
             peak[arm] = (torch.cuda.max_memory_allocated(), base)
+    launches, syncs = {}, {}
+    for arm in arms:
+        with _ffi.launch_log() as names:
+            step(arm)
+        launches[arm] = {n: names.count(n) for n in sorted(set(names))}
+        torch.cuda.synchronize()
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            torch.cuda.set_sync_debug_mode("warn")
+            step(arm)
+            torch.cuda.set_sync_debug_mode("default")
+        syncs[arm] = sum("synchroniz" in str(w.message).lower() for w in seen)
+        torch.cuda.synchronize()
     BasicMultiUpdateBlock.TRAIN_NODES = True
+    conv.GRAD_PREPASS = True
     out = {"B": B, "H": 4 * H, "W": 4 * W, "n_gru_layers": 3, "calls": ITERS, "steps": a.steps}
     for arm in arms:
         w = sorted(wall[arm])
         out["arm_" + arm] = {"wall_ms_median": round(w[len(w) // 2], 3), "wall_ms_min": round(w[0], 3),
                              "max_memory_allocated_MB": round(peak[arm][0] / 1e6, 1),
-                             "allocated_before_step_MB": round(peak[arm][1] / 1e6, 1)}
+                             "allocated_before_step_MB": round(peak[arm][1] / 1e6, 1),
+                             "host_syncs_per_step": syncs[arm], "library_launches_per_step": sum(launches[arm].values()),
+                             "library_launches": launches[arm]}
     if "a" in arms and "b" in arms:
         out["speedup_b_over_a"] = round(out["arm_a"]["wall_ms_median"] / out["arm_b"]["wall_ms_median"], 3)
+    if "b" in arms and "c" in arms:
+        out["speedup_c_over_b"] = round(out["arm_b"]["wall_ms_median"] / out["arm_c"]["wall_ms_median"], 3)
     if "b" in arms and not a.no_raw:
         out["raw_calls"] = raw_calls()
     print(json.dumps(out))
