@@ -671,8 +671,8 @@ def conv2d_gate_out(x, q_layer, cq, z, h, out=None):
 # Autograd of the stride-1 "same" convolution (training through the update operator, tools/ft_dkt.py:223-242): forward and
 # the input gradient run on this library's convolution kernels (the input gradient of a stride-1 same convolution is the
 # same convolution with the weights transposed over (Cout, Cin) and rotated by 180 degrees), the weight gradient -- a
-# reduction over all pixels, a different loop nest -- on the vendor library (torch.nn.grad.conv2d_weight), the bias gradient
-# is a sum.
+# reduction over all pixels, a different loop nest -- on dkt_conv2d_wgrad for 1x1 and 3x3 layers (GRAD_WEIGHT_HIP) and on the
+# vendor library (torch.nn.grad.conv2d_weight) for 7x7 ones, the bias gradient is a sum.
 #
 # Backward with GRAD_PREPASS (default): one streaming pre-pass (dkt_conv_grad_prepass) masks the upstream gradient with the
 # saved ReLU output, sums the bias gradient in a fixed order and leaves the RANGE of the masked gradient in device memory;
@@ -789,6 +789,41 @@ def conv2d_dscale(g, layer, scale, pack_scale=None):
     return out
 
 
+#: weight gradient of conv2d_autograd's 1x1 and 3x3 layers: True = dkt_conv2d_wgrad (csrc/conv_wgrad.hip), False = the vendor
+#: library (torch.nn.grad.conv2d_weight) fed with the same g' -- an A/B handle like GRAD_PREPASS; 7x7 layers, GRAD_PREPASS =
+#: False, CPU tensors and other dtypes stay on the vendor call either way
+GRAD_WEIGHT_HIP = True
+#: (Cin, Cout, K) classes that stay on the vendor call with the handle on: rows of `tools/bench_gru_train.py --wgrad` that lost
+#: to it at B = 2 (us of dkt_conv2d_wgrad vs us of the vendor call)
+WGRAD_VENDOR_CLASSES = {(64, 64, 3): "73.8 vs 71.0 at 120x224, 55.0 vs 51.7 at 60x112, 49.4 vs 38.6 at 30x56"}
+
+
+def conv2d_wgrad(x, g, scale, k, x_scale=1.0):
+    """dkt_conv2d_wgrad: the (Cout, Cin, k, k) weight gradient of a stride-1 "same" k x k convolution (k in {1, 3}) from its
+    input `x` (B, Cin, H, W) and the masked gradient `g` (B, Cout, H, W), both fp32 with dense batch elements (`g` may be a
+    view with a longer batch stride); `scale` is the device pair {2^e, 2^-e} conv_grad_prepass left for `g`, `x_scale` the
+    host power of two of the layer's forward activations.  Nothing is read back on the host."""
+    _ffi.require_gpu(x, g, scale)
+    B, cin, H, W = x.shape
+    cout = g.shape[1]
+    if tuple(g.shape) != (B, cout, H, W):
+        raise ValueError("conv2d_wgrad: g %s does not match x %s" % (tuple(g.shape), tuple(x.shape)))
+    if not _dense(x) or (B > 1 and x.stride(0) < cin * H * W):
+        x = x.contiguous()
+    if not _dense(g) or (B > 1 and g.stride(0) < cout * H * W):
+        g = g.contiguous()
+    L = _ffi.lib()
+    n = int(L.dkt_conv2d_wgrad_ws_floats(B, cin, cout, H, W, k))
+    if n < 0:
+        _ffi.check(n, "dkt_conv2d_wgrad_ws_floats")
+    gw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32)
+    ws = torch.empty(n, device=x.device, dtype=torch.float32)
+    rc = L.dkt_conv2d_wgrad(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(), float(x_scale),
+                            gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, k, _ffi.device_of(x), _ffi.stream_of(x))
+    _ffi.check(rc, "dkt_conv2d_wgrad")
+    return gw
+
+
 class _Conv2dGradFn(torch.autograd.Function):
     """conv2d_autograd with GRAD_PREPASS.  apply(x, relu, owner, nparts, *params): `owner` holds the (detached) weight and
     bias the kernels read and every packed image; `params` are the tensors autograd differentiates -- nparts weights, then
@@ -816,12 +851,16 @@ class _Conv2dGradFn(torch.autograd.Function):
             gy = gy if gy.dtype == torch.float32 else gy.float()
             shim = _grad_layer(ctx.owner) if need_x else None
             dscale = need_x and _dscale_eligible(shim)
+            wgrad = (need_w and GRAD_WEIGHT_HIP and kh == kw and kh in (1, 3) and x.is_cuda and gy.is_cuda
+                     and x.dtype == torch.float32 and (x.shape[1], w.shape[0], kh) not in WGRAD_VENDOR_CLASSES)
             g, scale = gy, None
-            if ctx.relu or need_b or dscale:
+            if ctx.relu or need_b or dscale or wgrad:
                 g, gb, scale = conv_grad_prepass(gy, y if ctx.relu else None, want_bias=need_b)
             if need_x:
                 gx = conv2d_dscale(g, shim, scale, shim.pack_scale) if dscale else conv2d(g, shim)
-            if need_w:
+            if wgrad:
+                gw = conv2d_wgrad(x.detach(), g, scale, kh, 2.0 ** in_exp_of(ctx.owner))
+            elif need_w:
                 gw = torch.nn.grad.conv2d_weight(x.detach(), w.shape, g, stride=1, padding=(kh // 2, kw // 2))
         gws = [None] * n if gw is None else list(gw.split(ctx.splits, 0)) if n > 1 else [gw]
         gbs = [None] * n if gb is None else list(gb.split(ctx.splits, 0)) if n > 1 else [gb]

@@ -389,6 +389,28 @@ int dkt_conv_grad_prepass(const float *gy, long gy_bstride, const float *y, long
                           float *gmask, float *gb, float *scale, float *ws,
                           int B, int C, long HW, int device, void *stream);
 
+/* dkt_conv2d_wgrad: the weight gradient of [relu](conv2d(x, w, b)), stride 1, "same" padding p = K/2, K in {1, 3}
+ * (core/update.py:9-10, 19-21, 72-76, 111-113 under training):
+ *   gw[co][ci][ky][kx] = sum_{b,y,x} g[b,co,y,x] * x[b,ci,y+ky-p,x+kx-p]
+ * x (B, Cin, H, W) and g (B, Cout, H, W; the masked gradient g') fp32 NCHW, every batch element dense, batch strides
+ * x_bstride / g_bstride (g may be the upstream gradient read in place); gw (Cout, Cin, K, K) dense fp32.
+ *   scale    the device pair {s, 1/s} of g as dkt_conv_grad_prepass writes it: g * s is split into fp16 hi + lo
+ *   x_scale  a host power of two: x * x_scale is split the same way (the layer's forward in_scale; 1 by default)
+ *   ws       dkt_conv2d_wgrad_ws_floats(B, Cin, Cout, H, W, K) floats of scratch, written before they are read
+ * Three v_mfma_f32_32x32x16_f16 products (g_hi*x_hi + g_lo*x_hi + g_hi*x_lo), fp32 accumulation, un-scaled by
+ * scale[1] / x_scale; every factor outside the fp16 operands is a power of two, so a power-of-two multiple of g gives that
+ * multiple of gw bit for bit.  The reduction is cut into slices (batch element x band of rows) by a rule of the shape alone,
+ * partial tiles go to ws and a finishing kernel adds a weight's slices in ascending order: no float atomics, bit-identical
+ * from run to run, for every grid size, and for the 16-byte (pointers, strides and W allow it) and the 4-byte load path.
+ * A non-finite g (pair e = 0) or x comes out non-finite.  The host reads nothing back.
+ * Errors, before any device is touched: x, g, scale, gw or ws null DKT_E_NULL; a size <= 0, K not in {1, 3}, a batch stride
+ * shorter than C*H*W, or x_scale not a positive finite power of two DKT_E_SHAPE. */
+long dkt_conv2d_wgrad_ws_floats(int B, int Cin, int Cout, int H, int W, int K);
+int dkt_conv2d_wgrad(const float *x, long x_bstride, const float *g, long g_bstride,
+                     const float *scale /* device {s, 1/s} of g */, float x_scale,
+                     float *gw /* (Cout,Cin,K,K) dense */, float *ws,
+                     int B, int Cin, int Cout, int H, int W, int K, int device, void *stream);
+
 /* dkt_conv2d_f16s (stride 1, no bias, no ReLU, no epilogue) with the activation scale in DEVICE memory: the input-gradient
  * convolution, whose operand range only the device knows.  scale = {s, 1/s} as dkt_conv_grad_prepass writes it:
  *   in_scale = scale[0],  out_scale = w_inv_scale * scale[1]   (w_inv_scale: 1 / the weight scale of the pack),

@@ -2,14 +2,16 @@
 """The update operator alone on the training path (BasicMultiUpdateBlock under autograd, tools/ft_dkt.py:223-242 of the
 reference) at the recipe shape of run_scripts/raft-stereo/ft_booster.sh: B = 2, 480 x 896 images, i.e. a 120 x 224 finest
 level, 3 GRU layers, 16 calls chained through the hidden states, forward and backward with a scalar loss on the 16 flow
-updates and masks; the weights are trainable (their gradient is the vendor library's in both arms).
+updates and masks; the weights are trainable (their gradient is the vendor library's in arms a to c).
 
   arm a  BasicMultiUpdateBlock.TRAIN_NODES = False: gates and resamplers as torch's expression sequence (training before
          the nodes);
   arm b  TRAIN_NODES = True: gru_train.gate_zr / gate_out / pool2x / interp (dkt_gru_gate_*_train, dkt_gru_gate_*_bwd,
          dkt_pool2x_bwd, dkt_interp_bilinear_bwd), the convolutions' backward as before conv.GRAD_PREPASS;
   arm c  arm b with conv.GRAD_PREPASS = True: dkt_conv_grad_prepass + dkt_conv2d_f16s_dscale, packed images held by their
-         owners (the default; on a tree without the handle arm b is that tree's only backward).
+         owners, conv.GRAD_WEIGHT_HIP = False: the weight gradient on the vendor library (on a tree without the handles arm b
+         is that tree's only backward);
+  arm d  arm c with conv.GRAD_WEIGHT_HIP = True: dkt_conv2d_wgrad for the 1x1 and 3x3 layers (the default).
 
 The arms alternate in one process after warm-up.  Per arm: wall ms of a step (host clock around a step that ends in a
 synchronise; median and minimum), torch.cuda.max_memory_allocated over a step, the library launches of a step's FORWARD by
@@ -23,6 +25,10 @@ would take.  Launch counts and kernel times come from a separate `rocprofv3 --ke
     python tools/bench_gru_train.py [--steps 10] [--warmup 3] [--arms a,b] [--no-raw]
     python tools/bench_gru_train.py --prepass   dkt_conv_grad_prepass alone at (2, 256, 120, 224), with and without y,
                                                 against its compulsory bytes
+    python tools/bench_gru_train.py --wgrad     one row per (level, layer) of the recipe block, B = 2: us of the vendor weight
+                                                gradient (HIP events around the whole torch.nn.grad.conv2d_weight call, its
+                                                transposes included, after a warm-up), us of dkt_conv2d_wgrad, algorithmic
+                                                GFLOP and the fraction of 833 TFLOP/s the new entry reaches
     python tools/bench_gru_train.py --gx-table  relative error of the input gradient of the z|r layer (1, 256 -> 384, 16 x 24)
                                                 against float64 at upstream gradients randn * 2^k, both backward paths
     python tools/bench_gru_train.py --sweep     worst error of the device's sigmoid (dkt_sigmoid) and tanhf against float64
@@ -158,6 +164,56 @@ def prepass_alone(sets=6, rounds=4, reps=5):
     print(json.dumps(out))
 
 
+#: (layer, Cin, Cout, K) of the recipe block's 1x1 and 3x3 layers
+WGRAD_LAYERS = [("z|r", 3 * CH, 2 * CH, 3), ("q", 3 * CH, CH, 3), ("flow_head.conv1", CH, 2 * CH, 3), ("flow_head.conv2", 2 * CH, 2, 3),
+                ("encoder.convc1", 36, 64, 1), ("encoder.convc2 / convf2", 64, 64, 3), ("encoder.conv", 128, 126, 3)]
+PEAK_SPLIT_FLOPS = 833e12
+
+
+def _event_us(fn, reps=5, rounds=8):
+    """Median over `reps` of the HIP-event time of `rounds` back-to-back calls, per call."""
+    us = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(rounds):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        us.append(e0.elapsed_time(e1) * 1e3 / rounds)
+    return sorted(us)[len(us) // 2]
+
+
+def wgrad_table():
+    """One JSON line per (level, layer): the vendor call against dkt_conv2d_wgrad on the same operands."""
+    lib = _ffi.lib()
+    p = lambda t: t.data_ptr()
+    for lvl in range(3):
+        h, w = H >> lvl, W >> lvl
+        for name, cin, cout, k in WGRAD_LAYERS:
+            torch.manual_seed(0)
+            x = torch.randn(B, cin, h, w, device="cuda")
+            g = torch.randn(B, cout, h, w, device="cuda") * 2.0 ** -10
+            _, _, scale = conv.conv_grad_prepass(g, None, want_bias=False)
+            gw = torch.empty(cout, cin, k, k, device="cuda")
+            ws = torch.empty(int(lib.dkt_conv2d_wgrad_ws_floats(B, cin, cout, h, w, k)), device="cuda")
+            dev, st = _ffi.device_of(x), _ffi.stream_of(x)
+            vendor = lambda: torch.nn.grad.conv2d_weight(x, (cout, cin, k, k), g, stride=1, padding=k // 2)
+            ours = lambda: lib.dkt_conv2d_wgrad(p(x), cin * h * w, p(g), cout * h * w, p(scale), 1.0, p(gw), p(ws), B, cin, cout,
+                                                h, w, k, dev, st)
+            for _ in range(3):                                  # warm-up: the vendor's kernel search is in neither figure
+                want = vendor()
+                _ffi.check(ours(), "dkt_conv2d_wgrad")
+            torch.cuda.synchronize()
+            rel = float((gw.double() - want.double()).abs().max() / want.double().abs().max())
+            v_us, o_us = _event_us(vendor), _event_us(ours)
+            gflop = 2.0 * B * h * w * cin * cout * k * k / 1e9
+            print(json.dumps({"level": "%dx%d" % (h, w), "layer": name, "cin": cin, "cout": cout, "k": k,
+                              "vendor_us": round(v_us, 1), "wgrad_us": round(o_us, 1), "gflop": round(gflop, 3),
+                              "frac_of_833TFLOPs": round(gflop * 1e9 / (o_us * 1e-6) / PEAK_SPLIT_FLOPS, 4),
+                              "ws_MB": round(ws.numel() * 4 / 1e6, 1), "rel_diff_to_vendor": float("%.3g" % rel)}), flush=True)
+
+
 def gx_table():
     """max|gx - exact| / max|exact| of the z|r layer's input gradient, exact = float64 on the device."""
     import torch.nn.functional as F
@@ -222,6 +278,7 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--prepass", action="store_true")
     ap.add_argument("--gx-table", action="store_true")
+    ap.add_argument("--wgrad", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_gru_train.py measures on a HIP device; none is available")
@@ -231,6 +288,8 @@ def main():
         return prepass_alone()
     if a.gx_table:
         return gx_table()
+    if a.wgrad:
+        return wgrad_table()
     arms = a.arms.split(",")
     blk = make_block()
     net0, inp, corr, flow, wd, wm = make_inputs()
@@ -238,7 +297,8 @@ def main():
 
     def step(arm):
         BasicMultiUpdateBlock.TRAIN_NODES = arm != "a"
-        conv.GRAD_PREPASS = arm == "c"
+        conv.GRAD_PREPASS = arm in ("c", "d")
+        conv.GRAD_WEIGHT_HIP = arm == "d"
         for t in params:
             t.grad = None
         net = [t.clone().requires_grad_(True) for t in net0]
@@ -281,6 +341,7 @@ def main():
         torch.cuda.synchronize()
     BasicMultiUpdateBlock.TRAIN_NODES = True
     conv.GRAD_PREPASS = True
+    conv.GRAD_WEIGHT_HIP = True
     out = {"B": B, "H": 4 * H, "W": 4 * W, "n_gru_layers": 3, "calls": ITERS, "steps": a.steps}
     for arm in arms:
         w = sorted(wall[arm])
@@ -293,6 +354,8 @@ def main():
         out["speedup_b_over_a"] = round(out["arm_a"]["wall_ms_median"] / out["arm_b"]["wall_ms_median"], 3)
     if "b" in arms and "c" in arms:
         out["speedup_c_over_b"] = round(out["arm_b"]["wall_ms_median"] / out["arm_c"]["wall_ms_median"], 3)
+    if "c" in arms and "d" in arms:
+        out["speedup_d_over_c"] = round(out["arm_c"]["wall_ms_median"] / out["arm_d"]["wall_ms_median"], 3)
     if "b" in arms and not a.no_raw:
         out["raw_calls"] = raw_calls()
     print(json.dumps(out))
