@@ -37,7 +37,7 @@ import threading
 import torch
 import torch.nn.functional as F
 
-from . import _ffi
+from . import _ffi, wcache
 
 import os as _os
 
@@ -45,7 +45,6 @@ _PASSES = {"f16x3": 3, "f16x2": 2, "f16": 1}
 _FEW_DIRECT = True
 _BACKEND = "f16x3"
 _TLS = threading.local()
-_CACHE_LOCK = threading.RLock()
 
 
 def _check_backend(name):
@@ -122,53 +121,13 @@ def _record_range(layer, srcs):
 
 
 class _Packed:
-    __slots__ = ("key", "hi", "lo", "inv_scale", "bias")
+    __slots__ = ("key", "src_channels", "hi", "lo", "inv_scale", "bias")
 
 
-def _packed_weights(layer, src_channels, scale=None):
-    """Split-fp16 weight image for dkt_conv2d_f16s, cached on the layer PER DEVICE (the shallow module
-    copies of nn.parallel.replicate share the cache dict; their parameters live on different devices)
-    and rebuilt when the parameter tensor is replaced or written.  `scale`: the power-of-two weight scale when
-    the caller already knows it (a rearrangement of a packed weight), else it is read from max|w| (a host sync)."""
-    with _CACHE_LOCK:
-        return _packed_weights_locked(layer, src_channels, scale)
-
-
-def _packed_weights_locked(layer, src_channels, scale=None):
-    w = layer.weight
-    b = layer.bias
-    key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version), tuple(src_channels))
-    cache = layer.__dict__.setdefault("_dkt_packed", {})
-    slot = (str(w.device), tuple(src_channels))
-    hit = cache.get(slot)
-    if hit is not None and hit.key == key:
-        return hit
-    cout, cin, kh, kw = w.shape
-    if cin != sum(src_channels):
-        raise ValueError("conv operands carry %d channels, layer expects %d" % (sum(src_channels), cin))
-    L = _ffi.lib()
-    n = len(src_channels)
-    ch = (ctypes.c_int * n)(*src_channels)
-    elems = L.dkt_conv2d_packed_elems(ch, n, cout, kh, kw)
-    if elems <= 0:
-        raise _ffi.DktError("dkt_conv2d_packed_elems rejected the layer shape")
-    if scale is None:
-        wmax = float(w.detach().abs().max())
-        # power-of-two scale putting max|w| in [2^12, 2^13): keeps w_lo out of the fp16 subnormals
-        e = 12 - math.floor(math.log2(wmax)) if wmax > 0 else 0
-        scale = 2.0 ** e
-    p = _Packed()
-    p.hi = torch.empty(elems, device=w.device, dtype=torch.float16)
-    p.lo = torch.empty(elems, device=w.device, dtype=torch.float16)
-    wc = w.detach().float().contiguous()
-    rc = L.dkt_conv2d_pack_weights(wc.data_ptr(), ch, n, cout, kh, kw, scale, p.hi.data_ptr(), p.lo.data_ptr(),
-                                   _ffi.device_of(w), _ffi.stream_of(w))
-    _ffi.check(rc, "dkt_conv2d_pack_weights")
-    p.inv_scale = 1.0 / scale
-    p.bias = None if b is None else b.detach().float().contiguous()
-    p.key = key
-    cache[slot] = p
-    return p
+def pack_scale(wmax):
+    """The power-of-two weight scale of a cold pack: max|w| lands in [2^12, 2^13), which keeps w_lo out of the fp16
+    subnormals."""
+    return 2.0 ** (12 - math.floor(math.log2(wmax))) if wmax > 0 else 1.0
 
 
 def _copy_unaliased(dst, src):
@@ -178,58 +137,112 @@ def _copy_unaliased(dst, src):
         dst.copy_(src.detach())
 
 
+def _new_packed(key, w, b, elems):
+    p = _Packed()
+    p.key = key
+    p.hi = torch.empty(elems, device=w.device, dtype=torch.float16)
+    p.lo = torch.empty(elems, device=w.device, dtype=torch.float16)
+    p.bias = None if b is None else b.detach().float().contiguous()
+    return p
+
+
+def _write_packed(p, layer, scale):
+    """The split-fp16 image of `layer`'s weight at `scale` into p's buffers, the bias into p.bias."""
+    w = layer.weight
+    n = len(p.src_channels)
+    ch = (ctypes.c_int * n)(*p.src_channels)
+    cout, _, kh, kw = w.shape
+    wc = w.detach().float().contiguous()
+    rc = _ffi.lib().dkt_conv2d_pack_weights(wc.data_ptr(), ch, n, cout, kh, kw, scale, p.hi.data_ptr(), p.lo.data_ptr(),
+                                            _ffi.device_of(w), _ffi.stream_of(w))
+    _ffi.check(rc, "dkt_conv2d_pack_weights")
+    p.inv_scale = 1.0 / scale
+    if p.bias is not None:
+        _copy_unaliased(p.bias, layer.bias)
+
+
+def _packed_weights(layer, src_channels, scale=None):
+    """Split-fp16 weight image for dkt_conv2d_f16s, cached on the layer per device and operand split and rebuilt when the
+    parameter tensor is replaced or written.  `scale`: the power-of-two weight scale when the caller already knows it (a
+    rearrangement of a packed weight), else it is read from max|w| (a host sync)."""
+    w = layer.weight
+    src_channels = tuple(src_channels)
+    key = wcache.key_of(w, layer.bias, extra=src_channels)
+    slot = (str(w.device), src_channels)
+    with wcache.LOCK:
+        hit = wcache.lookup(layer, "_dkt_packed", slot, key)
+        if hit is not None:
+            return hit
+        cout, cin, kh, kw = w.shape
+        if cin != sum(src_channels):
+            raise ValueError("conv operands carry %d channels, layer expects %d" % (sum(src_channels), cin))
+        n = len(src_channels)
+        elems = _ffi.lib().dkt_conv2d_packed_elems((ctypes.c_int * n)(*src_channels), n, cout, kh, kw)
+        if elems <= 0:
+            raise _ffi.DktError("dkt_conv2d_packed_elems rejected the layer shape")
+        if scale is None:
+            scale = pack_scale(float(w.detach().abs().max()))
+        p = _new_packed(key, w, layer.bias, elems)
+        p.src_channels = src_channels
+        _write_packed(p, layer, scale)
+        return wcache.store(layer, "_dkt_packed", slot, p)
+
+
 def _refresh_packed(layer, cache, R):
     """ema.ema_update_: rewrite the current split-fp16 images of `layer` in place, same buffers and scales."""
-    L = _ffi.lib()
-    for slot, p in list(cache.items()):
-        if not R.current(p.key):
-            continue
-        w, b = layer.weight, layer.bias
-        src_channels = p.key[3]
-        n = len(src_channels)
-        ch = (ctypes.c_int * n)(*src_channels)
-        cout, _, kh, kw = w.shape
-        wc = w.detach().float().contiguous()
-        R.window(R.amax(w), p.inv_scale, lambda c=cache, s=slot, q=p: c.pop(s) if c.get(s) is q else None)
-        rc = L.dkt_conv2d_pack_weights(wc.data_ptr(), ch, n, cout, kh, kw, 1.0 / p.inv_scale, p.hi.data_ptr(), p.lo.data_ptr(),
-                                       _ffi.device_of(w), _ffi.stream_of(w))
-        _ffi.check(rc, "dkt_conv2d_pack_weights")
-        if p.bias is not None:
-            _copy_unaliased(p.bias, b)
+    for p, drop in R.each(cache):
+        R.window(R.amax(layer.weight), p.inv_scale, drop)
+        _write_packed(p, layer, 1.0 / p.inv_scale)
         p.key = R.rekey(p.key)
 
 
+wcache.register("_dkt_packed", _refresh_packed)
+
+
+def _write_stem7(pk, layer, scale):
+    """The 7x7 stem image of `layer`'s weight at `scale` into pk's buffers, the bias into pk.bias."""
+    w = layer.weight
+    wc = w.detach().float().contiguous()
+    rc = _ffi.lib().dkt_conv2d_stem7_pack(wc.data_ptr(), w.shape[0], w.shape[1], scale, pk.hi.data_ptr(), pk.lo.data_ptr(),
+                                          _ffi.device_of(w), _ffi.stream_of(w))
+    _ffi.check(rc, "dkt_conv2d_stem7_pack")
+    pk.inv_scale = 1.0 / scale
+    if pk.bias is not None:
+        _copy_unaliased(pk.bias, layer.bias)
+
+
+def stem7_packed(layer):
+    """Split-fp16 image of a 7x7 stem for dkt_conv2d_stem7 and its C8S variants, cached on the layer per device."""
+    w = layer.weight
+    key = wcache.key_of(w, layer.bias)
+    slot = str(w.device)
+    with wcache.LOCK:
+        pk = wcache.lookup(layer, "_dkt_stem7", slot, key)
+        if pk is None:
+            scale = pack_scale(float(w.detach().abs().max()))
+            pk = _new_packed(key, w, layer.bias, _ffi.lib().dkt_conv2d_stem7_packed_elems(w.shape[0]))
+            _write_stem7(pk, layer, scale)
+            wcache.store(layer, "_dkt_stem7", slot, pk)
+    return pk
+
+
 def _refresh_stem7(layer, cache, R):
-    """ema.ema_update_: the 7x7 stem images of `layer` in place (see _stem7_packed)."""
-    L = _ffi.lib()
-    for slot, pk in list(cache.items()):
-        if not R.current(pk.key):
-            continue
-        w, b = layer.weight, layer.bias
-        cout, cin = w.shape[:2]
-        wc = w.detach().float().contiguous()
-        R.window(R.amax(w), pk.inv_scale, lambda c=cache, s=slot, q=pk: c.pop(s) if c.get(s) is q else None)
-        rc = L.dkt_conv2d_stem7_pack(wc.data_ptr(), cout, cin, 1.0 / pk.inv_scale, pk.hi.data_ptr(), pk.lo.data_ptr(),
-                                     _ffi.device_of(w), _ffi.stream_of(w))
-        _ffi.check(rc, "dkt_conv2d_stem7_pack")
-        if pk.bias is not None:
-            _copy_unaliased(pk.bias, b)
+    """ema.ema_update_: the 7x7 stem images of `layer` in place (see stem7_packed)."""
+    for pk, drop in R.each(cache):
+        R.window(R.amax(layer.weight), pk.inv_scale, drop)
+        _write_stem7(pk, layer, 1.0 / pk.inv_scale)
         pk.key = R.rekey(pk.key)
 
 
+wcache.register("_dkt_stem7", _refresh_stem7)
+
+
 def clear_weight_cache(module):
-    """Drops the packed fp16 weight images below `module` (needed only after writes
-    that bypass the Parameter's version counter, e.g. ``weight.data.mul_()``)."""
-    with _CACHE_LOCK:
-        for m in module.modules():
-            m.__dict__.pop("_dkt_packed", None)
-            m.__dict__.pop("_dkt_folded", None)
-            m.__dict__.pop("_dkt_stem7", None)
-            m.__dict__.pop("_dkt_wt", None)
-            m.__dict__.pop("_dkt_view", None)
-            m.__dict__.pop("_dkt_grad", None)
-            if hasattr(m, "_zr_cache"):
-                m._zr_cache = None
+    """Drops every cached weight derivative below `module` -- packed images of every kind, folded and merged layers, views,
+    copied weights, all that wcache's registry lists -- (needed only after writes that bypass the Parameter's version
+    counter, e.g. ``weight.data.mul_()``).  It used to leave the C8S step and ConvGRU images, the head weights, the merged
+    heads, the scaled layers and the encoder's C8S buffers in place, so the refinement loop kept running stale images."""
+    wcache.clear(module)
 
 
 def _dense(t):
@@ -241,6 +254,11 @@ def _stride_of(layer):
     st = getattr(layer, "stride", 1)
     st = (st, st) if isinstance(st, int) else tuple(st)
     return st
+
+
+def _padding_of(layer):
+    pad = layer.padding
+    return (pad, pad) if isinstance(pad, int) else tuple(pad)
 
 
 def _plain_conv(layer):
@@ -255,8 +273,7 @@ def hip_eligible(layer):
     """True when `layer` runs on dkt_conv2d_f16s[_strided] under the current backend:
     1x1 / 3x3, padding K/2, stride 1 or 2, no groups / dilation."""
     kh, kw = layer.weight.shape[2:]
-    pad = layer.padding
-    pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
+    pad = _padding_of(layer)
     return (get_backend() in _PASSES and kh == kw and kh in (1, 3) and pad == (kh // 2, kw // 2)
             and _stride_of(layer) in ((1, 1), (2, 2)) and _plain_conv(layer))
 
@@ -268,8 +285,7 @@ def direct_eligible(layer):
     if get_backend() not in _PASSES or not _plain_conv(layer):
         return False
     cout, cin, kh, kw = layer.weight.shape
-    pad = layer.padding
-    pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
+    pad = _padding_of(layer)
     if kh != kw or pad != (kh // 2, kw // 2) or _stride_of(layer) != (1, 1):
         return False
     return kh == 7 and cin <= 4
@@ -282,8 +298,7 @@ def few_eligible(layer):
     if get_backend() not in _PASSES or not _plain_conv(layer) or not _FEW_DIRECT:
         return False
     cout, cin, kh, kw = layer.weight.shape
-    pad = layer.padding
-    pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
+    pad = _padding_of(layer)
     if not (kh == 3 and kw == 3 and pad == (1, 1) and _stride_of(layer) == (1, 1) and cout <= 4):
         return False
     # what launch_few (conv_direct.hip) can stage in 160 KB of LDS: 110592 B of patches + 384 B per (8-channel slice, output);
@@ -352,45 +367,18 @@ def _conv2d_stem7(x, layer, relu, out):
     if not _dense(x):
         x = x.contiguous()
     B, cin, H, W = x.shape
-    w, b = layer.weight, layer.bias
-    cout = w.shape[0]
+    cout = layer.weight.shape[0]
     _record_range(layer, [x])
-    key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
-    L = _ffi.lib()
-    with _CACHE_LOCK:
-        pk = _stem7_packed(layer, key, L)
+    pk = stem7_packed(layer)
     in_scale = 2.0 ** in_exp_of(layer)
     if out is None:
         out = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32)
-    rc = L.dkt_conv2d_stem7(x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
-                            None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
-                            out.data_ptr(), out.stride(0), B, cin, cout, H, W, int(bool(relu)),
-                            _ffi.device_of(x), _ffi.stream_of(x))
+    rc = _ffi.lib().dkt_conv2d_stem7(x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
+                                     None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
+                                     out.data_ptr(), out.stride(0), B, cin, cout, H, W, int(bool(relu)),
+                                     _ffi.device_of(x), _ffi.stream_of(x))
     _ffi.check(rc, "dkt_conv2d_stem7")
     return out
-
-
-def _stem7_packed(layer, key, L):
-    w, b = layer.weight, layer.bias
-    cout, cin = w.shape[:2]
-    cache = layer.__dict__.setdefault("_dkt_stem7", {})
-    pk = cache.get(str(w.device))
-    if pk is None or pk.key != key:
-        wmax = float(w.detach().abs().max())
-        scale = 2.0 ** (12 - math.floor(math.log2(wmax)) if wmax > 0 else 0)
-        pk = _Packed()
-        n = L.dkt_conv2d_stem7_packed_elems(cout)
-        pk.hi = torch.empty(n, device=w.device, dtype=torch.float16)
-        pk.lo = torch.empty(n, device=w.device, dtype=torch.float16)
-        wc = w.detach().float().contiguous()
-        rc = L.dkt_conv2d_stem7_pack(wc.data_ptr(), cout, cin, scale, pk.hi.data_ptr(), pk.lo.data_ptr(),
-                                     _ffi.device_of(w), _ffi.stream_of(w))
-        _ffi.check(rc, "dkt_conv2d_stem7_pack")
-        pk.inv_scale = 1.0 / scale
-        pk.bias = None if b is None else b.detach().float().contiguous()
-        pk.key = key
-        cache[str(w.device)] = pk
-    return pk
 
 
 class _Operands:
@@ -680,7 +668,7 @@ def conv2d_gate_out(x, q_layer, cq, z, h, out=None):
 # magnitude -- 1e-6 from a mean-reduced loss, 1e+6 under a loss scale -- keeps the ~22 bits of the split instead of the
 # format's absolute 2^-25 floor, and a power-of-two multiple of the upstream gradient gives that multiple of gx and gb bit
 # for bit.  The host reads nothing back.  The packed images of both orientations live on a persistent OWNER (the nn.Module,
-# or ConvGRU._merged_zr() for z|r), keyed on the weight's (data_ptr, _version): packed once per optimizer step, not per call.
+# or ConvGRU._merged_zr() for z|r), keyed on the weight's wcache.Key: packed once per optimizer step, not per call.
 # ---------------------------------------------------------------------------------------------------------------------
 #: backward of conv2d_autograd: True = pre-pass + device-scaled input gradient + owner-held packs; False = the sequence
 #: before them (the A/B handle of tools/bench_gru_train.py, in the style of BasicMultiUpdateBlock.TRAIN_NODES)
@@ -726,24 +714,28 @@ class _Conv2dFn(torch.autograd.Function):
 
 def _grad_layer(owner):
     """The layer of the input gradient -- `owner`'s weight transposed over (Cout, Cin) and rotated by 180 degrees -- as a
-    persistent object on `owner`, per device, keyed on the weight's (data_ptr, _version); its own packed image hangs off it
+    persistent object on `owner`, per device, keyed on the weight's wcache.Key; its own packed image hangs off it
     (_packed_weights) and takes the scale of the forward image (the same max|w|: no host read)."""
     w = owner.weight
-    key = (w.data_ptr(), w._version)
-    with _CACHE_LOCK:
-        cache = owner.__dict__.setdefault("_dkt_grad", {})
-        hit = cache.get(str(w.device))
-        if hit is not None and hit[0] == key:
-            return hit[1]
+    key = wcache.key_of(w)
+    slot = str(w.device)
+    with wcache.LOCK:
+        hit = wcache.lookup(owner, "_dkt_grad", slot, key)
+        if hit is not None:
+            return hit.value
         kh, kw = w.shape[2:]
         with torch.no_grad():
             shim = _LayerShim(w.detach().float().transpose(0, 1).flip(2, 3).contiguous(), None, (kh // 2, kw // 2))
         shim.pack_scale = None
-        for p in owner.__dict__.get("_dkt_packed", {}).values():
-            if p.key[:2] == key:
-                shim.pack_scale = 1.0 / p.inv_scale
-        cache[str(w.device)] = (key, shim)
+        for lst in owner.__dict__.get("_dkt_packed", {}).values():
+            for p in lst:
+                if p.key.tensors[0] == key.tensors[0]:
+                    shim.pack_scale = 1.0 / p.inv_scale
+        wcache.store(owner, "_dkt_grad", slot, wcache.Entry(key, shim))
         return shim
+
+
+wcache.register("_dkt_grad", weights=False)
 
 
 def _dscale_eligible(shim):
@@ -872,8 +864,7 @@ class _Conv2dGradFn(torch.autograd.Function):
 def _autograd_eligible(x, layer):
     """fp32 HIP tensor, stride-1 "same" layer with an odd square kernel, no groups / dilation."""
     kh, kw = layer.weight.shape[2:]
-    pad = layer.padding
-    pad = (pad, pad) if isinstance(pad, int) else tuple(pad)
+    pad = _padding_of(layer)
     return (x.is_cuda and x.dtype == torch.float32 and kh == kw and kh % 2 == 1 and pad == (kh // 2, kw // 2)
             and _stride_of(layer) == (1, 1) and _plain_conv(layer))
 

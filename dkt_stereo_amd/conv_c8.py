@@ -5,13 +5,14 @@
 ``pack`` / ``unpack`` convert from / to fp32 NCHW for glue and tests.  Reference operators: ConvGRU
 (core/update.py:16-32), BasicMotionEncoder (:64-85), FlowHead.conv1 (:9)."""
 import ctypes
-import math
 import threading
 
 import torch
 
 from . import _ffi
-from .conv import _CACHE_LOCK, _copy_unaliased
+from . import wcache
+from .conv import _copy_unaliased, pack_scale
+from .wcache import pin_packs       # (its users name it conv_c8.pin_packs)
 
 
 def c8_dims(H, W):
@@ -103,7 +104,7 @@ def unpack(a, C=None, ch0=0):
 
 
 class _PackedC8:
-    __slots__ = ("key", "img", "inv_scale", "bias")
+    __slots__ = ("key", "src_channels", "scales", "img", "inv_scale", "bias")
 
 
 #: packed images kept per (layer, device, operand split): one per set of operand scales in use.  Two captured loops over the
@@ -113,7 +114,6 @@ class _PackedC8:
 _PACK_KEEP = 6
 
 
-_PINS = threading.local()
 _PASSES = threading.local()
 
 
@@ -142,44 +142,6 @@ def current_passes():
     return getattr(_PASSES, "n", 3)
 
 
-class pin_packs:
-    """Every packed image looked up or made on this thread inside the block is appended to `keep` (strong references): a
-    captured graph bakes the images' addresses in, while the per-layer caches evict beyond _PACK_KEEP entries -- the capturing
-    loop holds what its graphs point to until it drops them (another thread's recalibrations could free them)."""
-
-    def __init__(self, keep):
-        self.keep = keep
-
-    def __enter__(self):
-        self.prev = getattr(_PINS, "keep", None)
-        _PINS.keep = self.keep
-        return self.keep
-
-    def __exit__(self, *exc):
-        _PINS.keep = self.prev
-        return False
-
-
-def _pinned(p):
-    keep = getattr(_PINS, "keep", None)
-    if keep is not None and p is not None:
-        keep.append(p)
-    return p
-
-
-def _cache_get(cache, slot, key):
-    for p in cache.get(slot, ()):
-        if p.key == key:
-            return _pinned(p)
-    return None
-
-
-def _cache_put(cache, slot, p, n_weight_keys):
-    _pinned(p)
-    keep = [q for q in cache.get(slot, ()) if q.key[:n_weight_keys] == p.key[:n_weight_keys]]
-    cache[slot] = (keep + [p])[-_PACK_KEEP:]
-
-
 def _in_scale_vector(seg_lists, device):
     """1 / scale per input channel for operands whose channel_scales() are `seg_lists` (None when every scale is 1)."""
     segs = [sg for lst in seg_lists for sg in lst]
@@ -188,68 +150,78 @@ def _in_scale_vector(seg_lists, device):
     return torch.cat([torch.full((n,), 1.0 / sc, device=device, dtype=torch.float32) for n, sc in segs])
 
 
+def _scaled_weight(layer, scales):
+    """`layer`'s weight in fp32 with 1 / scale of its operands' channels folded in (powers of two: exact)."""
+    wc = layer.weight.detach().float()
+    if scales is not None:
+        wc = wc * _in_scale_vector(scales, wc.device).view(1, -1, 1, 1)
+    return wc
+
+
 def packed_weights(layer, src_channels, src_scales=None):
     """Step images of `layer` for dkt_conv2d_c8, cached on the layer per device and operand split.  `src_scales`: the
-    operands' channel_scales(); their inverses are folded into the weights (powers of two: exact)."""
-    with _CACHE_LOCK:
-        w, b = layer.weight, layer.bias
-        scales = tuple(tuple(x) for x in src_scales) if src_scales is not None else None
-        if scales is not None and all(sc == 1.0 for lst in scales for _, sc in lst):
-            scales = None
-        key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version), tuple(src_channels), scales)
-        cache = layer.__dict__.setdefault("_dkt_packed_c8", {})
-        slot = (str(w.device), tuple(src_channels))
-        hit = _cache_get(cache, slot, key)
+    operands' channel_scales(); their inverses are folded into the weights."""
+    w, b = layer.weight, layer.bias
+    src_channels = tuple(src_channels)
+    scales = tuple(tuple(x) for x in src_scales) if src_scales is not None else None
+    if scales is not None and all(sc == 1.0 for lst in scales for _, sc in lst):
+        scales = None
+    key = wcache.key_of(w, b, extra=(src_channels, scales))
+    slot = (str(w.device), src_channels)
+    with wcache.LOCK:
+        hit = wcache.lookup(layer, "_dkt_packed_c8", slot, key)
         if hit is not None:
             return hit
-        cout, cin, kh, kw = w.shape
-        if (kh, kw) != (3, 3) or cin != sum(src_channels):
-            raise ValueError("conv2d_c8: 3x3 layers only, operands carry %d channels, layer expects %d" % (sum(src_channels), cin))
-        L = _ffi.lib()
-        n = len(src_channels)
-        ch = (ctypes.c_int * n)(*src_channels)
-        nbytes = L.dkt_conv_c8_packed_bytes(ch, n, cout)
-        if nbytes <= 0:
-            raise _ffi.DktError("dkt_conv_c8_packed_bytes rejected the layer shape")
-        wc = w.detach().float()
-        if scales is not None:
-            wc = wc * _in_scale_vector(scales, w.device).view(1, -1, 1, 1)
-        wc = wc.contiguous()
-        wmax = float(wc.abs().max())
-        e = 12 - math.floor(math.log2(wmax)) if wmax > 0 else 0       # max|w| in [2^12, 2^13): w_lo stays normal
+        if w.shape[1] != sum(src_channels):                       # (before the scales are folded along that axis)
+            raise ValueError("conv2d_c8: operands carry %d channels, layer expects %d" % (sum(src_channels), w.shape[1]))
         p = _PackedC8()
-        p.img = torch.zeros(nbytes // 2, device=w.device, dtype=torch.float16)
-        rc = L.dkt_conv_c8_pack_weights(wc.data_ptr(), ch, n, cout, 2.0 ** e, p.img.data_ptr(), _ffi.device_of(w), _ffi.stream_of(w))
-        _ffi.check(rc, "dkt_conv_c8_pack_weights")
-        p.inv_scale = 2.0 ** -e
+        p.key, p.src_channels, p.scales = key, src_channels, scales
+        p.img, p.inv_scale = _pack_raw(_scaled_weight(layer, scales), src_channels)
         p.bias = None if b is None else b.detach().float().contiguous()
-        p.key = key
-        _cache_put(cache, slot, p, 3)
-        return p
+        return wcache.store(layer, "_dkt_packed_c8", slot, p, _PACK_KEEP)
 
 
 def _pack_raw(w, src_channels):
     """(Cout, Cin, 3, 3) fp32 -> (step images, 1 / weight scale) for sources of `src_channels` channels (Cin in that order)."""
-    L = _ffi.lib()
     cout, cin = int(w.shape[0]), int(w.shape[1])
     if tuple(w.shape[2:]) != (3, 3) or cin != sum(src_channels):
         raise ValueError("conv_c8: 3x3 layers only, operands carry %d channels, layer expects %d" % (sum(src_channels), cin))
     n = len(src_channels)
-    ch = (ctypes.c_int * n)(*src_channels)
-    nbytes = L.dkt_conv_c8_packed_bytes(ch, n, cout)
+    nbytes = _ffi.lib().dkt_conv_c8_packed_bytes((ctypes.c_int * n)(*src_channels), n, cout)
     if nbytes <= 0:
         raise _ffi.DktError("dkt_conv_c8_packed_bytes rejected the layer shape")
-    wmax = float(w.abs().max())
-    e = 12 - math.floor(math.log2(wmax)) if wmax > 0 else 0
+    inv_scale = 1.0 / pack_scale(float(w.abs().max()))
     img = torch.zeros(nbytes // 2, device=w.device, dtype=torch.float16)
+    _repack_raw(w, src_channels, inv_scale, img)
+    return img, inv_scale
+
+
+def _repack_raw(w, src_channels, inv_scale, img):
+    """The step images of `w` at 1 / inv_scale into `img`: the one writer of the C8S layer and ConvGRU images."""
+    n = len(src_channels)
+    ch = (ctypes.c_int * n)(*src_channels)
     wc = w.float().contiguous()
-    rc = L.dkt_conv_c8_pack_weights(wc.data_ptr(), ch, n, cout, 2.0 ** e, img.data_ptr(), _ffi.device_of(w), _ffi.stream_of(w))
+    rc = _ffi.lib().dkt_conv_c8_pack_weights(wc.data_ptr(), ch, n, int(w.shape[0]), 1.0 / inv_scale, img.data_ptr(),
+                                             _ffi.device_of(w), _ffi.stream_of(w))
     _ffi.check(rc, "dkt_conv_c8_pack_weights")
-    return img, 2.0 ** -e
+
+
+def _refresh_packed_c8(layer, cache, R):
+    """ema.ema_update_: the current step images of `layer` rewritten in place with their scales (see packed_weights)."""
+    for p, drop in R.each(cache):
+        wc = _scaled_weight(layer, p.scales)
+        R.window(R.amax(layer.weight) if p.scales is None else wc.abs().amax(), p.inv_scale, drop)
+        _repack_raw(wc, p.src_channels, p.inv_scale, p.img)
+        if p.bias is not None:
+            _copy_unaliased(p.bias, layer.bias)
+        p.key = R.rekey(p.key)
+
+
+wcache.register("_dkt_packed_c8", _refresh_packed_c8, pinned=True)
 
 
 class _PackedGru:
-    __slots__ = ("key", "wzr", "wq", "inv_zr", "inv_q", "bz", "br", "bq")
+    __slots__ = ("key", "x_channels", "hs", "xs", "wzr", "wq", "inv_zr", "inv_q", "bz", "br", "bq")
 
 
 def _gru_images(gru, x_channels, hs, xs):
@@ -271,92 +243,39 @@ def gru_packed(gru, x_channels, h_scales=None, x_scales=None):
     blocks of 32 (a wave holds z and r of the same hidden channels), the q image with its input channels reordered to
     [x... | r*h] (the x chunks are consumed before the neighbours' r*h is needed).  `h_scales` / `x_scales`: channel_scales()
     of the state (= of r*h) and of the x operands, folded into the weights.  Cached on the module per device."""
-    with _CACHE_LOCK:
-        ps = [gru.convz.weight, gru.convr.weight, gru.convq.weight, gru.convz.bias, gru.convr.bias, gru.convq.bias]
-        hs = tuple(h_scales) if h_scales is not None else ((128, 1.0),)
-        xs = tuple(tuple(x) for x in x_scales) if x_scales is not None else tuple(((c, 1.0),) for c in x_channels)
-        key = tuple((p.data_ptr(), p._version) for p in ps) + (tuple(x_channels), hs, xs)
-        cache = gru.__dict__.setdefault("_dkt_gru_c8", {})
-        slot = (str(ps[0].device), tuple(x_channels))
-        hit = _cache_get(cache, slot, key)
+    ps = [gru.convz.weight, gru.convr.weight, gru.convq.weight, gru.convz.bias, gru.convr.bias, gru.convq.bias]
+    x_channels = tuple(x_channels)
+    hs = tuple(h_scales) if h_scales is not None else ((128, 1.0),)
+    xs = tuple(tuple(x) for x in x_scales) if x_scales is not None else tuple(((c, 1.0),) for c in x_channels)
+    key = wcache.key_of(*ps, extra=(x_channels, hs, xs))
+    slot = (str(ps[0].device), x_channels)
+    with wcache.LOCK:
+        hit = wcache.lookup(gru, "_dkt_gru_c8", slot, key)
         if hit is not None:
             return hit
         wzr, wq2, ch = _gru_images(gru, x_channels, hs, xs)
         p = _PackedGru()
+        p.key, p.x_channels, p.hs, p.xs = key, x_channels, hs, xs
         p.wzr, p.inv_zr = _pack_raw(wzr, [ch] + list(x_channels))
         p.wq, p.inv_q = _pack_raw(wq2, list(x_channels) + [ch])
         p.bz, p.br, p.bq = (b.detach().float().contiguous() for b in ps[3:])
-        p.key = key
-        _cache_put(cache, slot, p, 6)
-        return p
-
-
-def _repack_raw(w, src_channels, inv_scale, img):
-    """_pack_raw into an existing image with a given scale (ema.ema_update_)."""
-    L = _ffi.lib()
-    n = len(src_channels)
-    ch = (ctypes.c_int * n)(*src_channels)
-    wc = w.float().contiguous()
-    rc = L.dkt_conv_c8_pack_weights(wc.data_ptr(), ch, n, int(w.shape[0]), 1.0 / inv_scale, img.data_ptr(),
-                                    _ffi.device_of(w), _ffi.stream_of(w))
-    _ffi.check(rc, "dkt_conv_c8_pack_weights")
-
-
-def _dropper(cache, slot, p):
-    def drop():
-        lst = [q for q in cache.get(slot, ()) if q is not p]
-        if lst:
-            cache[slot] = lst
-        else:
-            cache.pop(slot, None)
-    return drop
-
-
-def _refresh_packed_c8(layer, cache, R):
-    """ema.ema_update_: the current step images of `layer` rewritten in place with their scales (see packed_weights)."""
-    for slot, lst in list(cache.items()):
-        for p in list(lst):
-            if not R.current(p.key):
-                continue
-            w, b = layer.weight, layer.bias
-            src_channels, scales = p.key[3], p.key[4]
-            wc = w.detach().float()
-            amax = R.amax(w)
-            if scales is not None:
-                wc = wc * _in_scale_vector(scales, w.device).view(1, -1, 1, 1)
-                amax = wc.abs().amax()
-            R.window(amax, p.inv_scale, _dropper(cache, slot, p))
-            _repack_raw(wc, src_channels, p.inv_scale, p.img)
-            if p.bias is not None:
-                _copy_unaliased(p.bias, b)
-            p.key = R.rekey(p.key)
+        return wcache.store(gru, "_dkt_gru_c8", slot, p, _PACK_KEEP)
 
 
 def _refresh_gru_c8(gru, cache, R):
     """ema.ema_update_: the z|r and q images of one ConvGRU rewritten in place with their scales (see gru_packed)."""
-    for slot, lst in list(cache.items()):
-        for p in list(lst):
-            if not R.current(p.key):
-                continue
-            x_channels, hs, xs = p.key[6:9]
-            wzr, wq2, ch = _gru_images(gru, x_channels, hs, xs)
-            drop = _dropper(cache, slot, p)
-            R.window(wzr.abs().amax(), p.inv_zr, drop)
-            R.window(wq2.abs().amax(), p.inv_q, drop)
-            _repack_raw(wzr, [ch] + list(x_channels), p.inv_zr, p.wzr)
-            _repack_raw(wq2, list(x_channels) + [ch], p.inv_q, p.wq)
-            for dst, src in zip((p.bz, p.br, p.bq), (gru.convz.bias, gru.convr.bias, gru.convq.bias)):
-                _copy_unaliased(dst, src)
-            p.key = R.rekey(p.key)
+    for p, drop in R.each(cache):
+        wzr, wq2, ch = _gru_images(gru, p.x_channels, p.hs, p.xs)
+        R.window(wzr.abs().amax(), p.inv_zr, drop)
+        R.window(wq2.abs().amax(), p.inv_q, drop)
+        _repack_raw(wzr, [ch] + list(p.x_channels), p.inv_zr, p.wzr)
+        _repack_raw(wq2, list(p.x_channels) + [ch], p.inv_q, p.wq)
+        for dst, src in zip((p.bz, p.br, p.bq), (gru.convz.bias, gru.convr.bias, gru.convq.bias)):
+            _copy_unaliased(dst, src)
+        p.key = R.rekey(p.key)
 
 
-def _refresh_head_w(layer2, cache, R):
-    """ema.ema_update_: the head's second-layer weights (see _head_weights) rewritten in place."""
-    for dev, (key, t) in list(cache.items()):
-        if R.current(key):
-            w = layer2.weight
-            t[:, :, :9].copy_(w.detach().float().reshape(w.shape[0], w.shape[1], 9))
-            cache[dev] = (R.rekey(key), t)
+wcache.register("_dkt_gru_c8", _refresh_gru_c8, pinned=True)
 
 
 def gru_flags(B, H, W, device):
@@ -568,11 +487,9 @@ def stem7_c8(x, layer, dst, relu=True, ch0=0):
     """dst[ch0 : ...] = C8S([relu](conv7x7(x))) for the 2- / 1-channel stems (core/update.py:75)."""
     from . import conv as _conv
     B, cin, H, W = x.shape
-    w, b = layer.weight, layer.bias
-    key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
+    w = layer.weight
     L = _ffi.lib()
-    with _CACHE_LOCK:
-        pk = _conv._stem7_packed(layer, key, L)
+    pk = _conv.stem7_packed(layer)
     in_scale = 2.0 ** _conv.in_exp_of(layer)
     if int(w.shape[0]) % 64:
         raise ValueError("stem7_c8: the C8S store writes whole 64-channel blocks (layer has %d outputs)" % int(w.shape[0]))
@@ -585,18 +502,31 @@ def stem7_c8(x, layer, dst, relu=True, ch0=0):
     return dst
 
 
+def _write_head_w(e, layer2):
+    w = layer2.weight
+    e.value[:, :, :9].copy_(w.detach().float().reshape(w.shape[0], w.shape[1], 9))
+
+
 def _head_weights(layer2):
     """(n_out, Cout, 3, 3) weights of the head's second layer as [n_out][Cout][12] fp32 (cached per device / version)."""
     w = layer2.weight
-    key = (w.data_ptr(), w._version)
-    with _CACHE_LOCK:
-        cache = layer2.__dict__.setdefault("_dkt_head_w", {})
-        hit = cache.get(str(w.device))
-        if hit is None or hit[0] != key:
-            t = torch.zeros((w.shape[0], w.shape[1], 12), device=w.device, dtype=torch.float32)
-            t[:, :, :9] = w.detach().float().reshape(w.shape[0], w.shape[1], 9)
-            hit = cache[str(w.device)] = (key, t)
-        return hit[1]
+
+    def build(key):
+        e = wcache.Entry(key, torch.zeros((w.shape[0], w.shape[1], 12), device=w.device, dtype=torch.float32))
+        _write_head_w(e, layer2)
+        return e
+    return wcache.cached(layer2, "_dkt_head_w", str(w.device), wcache.key_of(w), build).value
+
+
+def _refresh_head_w(layer2, cache, R):
+    """ema.ema_update_: the head's second-layer weights (see _head_weights) rewritten in place."""
+    for e, _ in R.each(cache):
+        _write_head_w(e, layer2)
+        e.key = R.rekey(e.key)
+    return []
+
+
+wcache.register("_dkt_head_w", _refresh_head_w, derived=True)
 
 
 def head_planes(srcs, layer1, layer2, cfg=2):
@@ -641,10 +571,8 @@ def motion_front(corr, planes, n_co, head_bias, x_old, x_new, x0, flow, convc1, 
     if x_new.data_ptr() == x_old.data_ptr():
         raise ValueError("motion_front: x_new must not alias x_old")
     L = _ffi.lib()
-    wf, bf = convf1.weight, convf1.bias
-    key = (wf.data_ptr(), wf._version, None if bf is None else (bf.data_ptr(), bf._version))
-    with _CACHE_LOCK:
-        pk = _conv._stem7_packed(convf1, key, L)
+    wf = convf1.weight
+    pk = _conv.stem7_packed(convf1)
     in_scale = 2.0 ** _conv.in_exp_of(convf1)
     wm = _kmajor_weight(convc1)
     bc = convc1.bias
@@ -699,11 +627,9 @@ def stem7_dual(x, layer, out, dst, relu=True):
     core/extractor.py:140-142 / :167-171 with an eval-mode BatchNorm folded into `layer`)."""
     from . import conv as _conv
     B, cin, H, W = x.shape
-    w, b = layer.weight, layer.bias
-    key = (w.data_ptr(), w._version, None if b is None else (b.data_ptr(), b._version))
+    w = layer.weight
     L = _ffi.lib()
-    with _CACHE_LOCK:
-        pk = _conv._stem7_packed(layer, key, L)
+    pk = _conv.stem7_packed(layer)
     in_scale = 2.0 ** _conv.in_exp_of(layer)
     rc = L.dkt_conv2d_stem7_dual(x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
                                  None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,

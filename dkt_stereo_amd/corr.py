@@ -16,13 +16,10 @@ the reference's grid_sample / avg_pool2d / einsum chain.  Coordinates must be de
 reference's callers do (raft_stereo.py:152).  The other classes are inference only.
 """
 import os
-import threading
 
 import torch
 
-from . import _ffi
-
-_WT_LOCK = threading.Lock()
+from . import _ffi, wcache
 
 
 def _build_pyramid(fmap1, fmap2, num_levels, divisor, out=None):
@@ -265,24 +262,21 @@ def _kmajor_weight(layer):
     version (under the lock: a thread that lost a creation race would otherwise free the tensor another thread's captured
     graph already points to)."""
     w = layer.weight
-    key = (w.data_ptr(), w._version)
-    with _WT_LOCK:
-        cache = layer.__dict__.setdefault("_dkt_wt", {})
-        hit = cache.get(str(w.device))
-        if hit is None or hit[0] != key:
-            hit = cache[str(w.device)] = (key, w.detach().reshape(w.shape[0], -1).t().float().contiguous())
-    return hit[1]
+    return wcache.cached(layer, "_dkt_wt", str(w.device), wcache.key_of(w), lambda key: wcache.Entry(
+        key, w.detach().reshape(w.shape[0], -1).t().float().contiguous())).value
 
 
 def _refresh_kmajor(layer, cache, R):
-    """ema.ema_update_: the k-major copy of a 1x1 layer's weight (_kmajor_weight; geometry's lookup keeps the same one)
-    rewritten in place."""
-    for dev, (key, wm) in list(cache.items()):
-        if R.current(key):
-            w = layer.weight
-            from .conv import _copy_unaliased
-            _copy_unaliased(wm, w.detach().reshape(w.shape[0], -1).t())
-            cache[dev] = (R.rekey(key), wm)
+    """ema.ema_update_: the k-major copy of a 1x1 layer's weight (_kmajor_weight) rewritten in place."""
+    for e, _ in R.each(cache):
+        w = layer.weight
+        if e.value.data_ptr() != w.data_ptr():              # (as conv._copy_unaliased)
+            e.value.copy_(w.detach().reshape(w.shape[0], -1).t())
+        e.key = R.rekey(e.key)
+    return []
+
+
+wcache.register("_dkt_wt", _refresh_kmajor, derived=True)
 
 
 class CorrBlockFast1D(CorrBlock1D):

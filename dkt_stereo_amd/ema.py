@@ -23,40 +23,12 @@ import torch
 import torch.nn as nn
 
 from . import _ffi
-from . import conv as _conv
-from . import conv_c8 as _conv_c8
-from . import corr as _corr
-from . import extractor as _extractor
-from . import update as _update
+# (importing the modules that fill the caches registers their refreshers)
+from . import conv, conv_c8, corr, extractor, update      # noqa: F401
+from .wcache import DERIVED_HOOKS, NOT_WEIGHTS, PACK_HOOKS
 
 #: scaled max|w| window of a refreshed pack: [2^WINDOW_LO, 2^WINDOW_HI)
 WINDOW_LO, WINDOW_HI = 11, 14
-
-
-def _zr(module, cache, R):
-    return module._refresh_zr(cache, R)
-
-
-#: derived-weight caches: refreshed first; each returns the derived layers, whose own pack caches are refreshed next
-DERIVED_HOOKS = {
-    "_dkt_folded": _extractor._refresh_folded,
-    "_dkt_merged": _extractor._refresh_merged,
-    "_zr_cache": _zr,
-    "_dkt_view": lambda layer, view, R: [v for v in [_update._refresh_view(layer, view, R)] if v is not None],
-    "_dkt_scaled": lambda layer, view, R: [v for v in [_update._refresh_view(layer, view, R)] if v is not None],
-    "_dkt_wt": lambda layer, cache, R: _corr._refresh_kmajor(layer, cache, R) or [],
-    "_dkt_head_w": lambda layer, cache, R: _conv_c8._refresh_head_w(layer, cache, R) or [],
-}
-#: packed images (split-fp16, C8S, ConvGRU, 7x7 stem): rewritten with the pack kernels at their cached scales
-PACK_HOOKS = {
-    "_dkt_packed": _conv._refresh_packed,
-    "_dkt_stem7": _conv._refresh_stem7,
-    "_dkt_packed_c8": _conv_c8._refresh_packed_c8,
-    "_dkt_gru_c8": _conv_c8._refresh_gru_c8,
-}
-#: per-layer caches that hold no weight derivative, or one that no captured launch reads and that is keyed on the weight's
-#: version, i.e. rebuilt by its next use (the input-gradient images of conv.conv2d_autograd's backward)
-NOT_WEIGHTS = {"_dkt_c8_buf", "_dkt_grad"}
 
 
 class _Refresh:
@@ -71,33 +43,38 @@ class _Refresh:
         self.index = {}           # data_ptr -> (position in absmax, numel) of the kernel's parameters
         self.repacked = 0
 
-    def _pairs(self, key):
-        if isinstance(key, tuple):
-            for i, x in enumerate(key):
-                if type(x) is int and i + 1 < len(key) and type(key[i + 1]) is int and (x in self.vmap or x in self.gone):
-                    yield i, x, key[i + 1]
-                elif isinstance(x, tuple):
-                    yield from self._pairs(x)
-
     def current(self, key):
         """True when `key` names at least one written tensor and every one at the version it had before this update."""
         seen = False
-        for _, ptr, ver in self._pairs(key):
-            if ptr in self.gone or self.vmap[ptr][0] != ver:
+        for t in key.tensors:
+            if t is None:
+                continue
+            if t[0] in self.gone:
                 return False
-            seen = True
+            ver = self.vmap.get(t[0])
+            if ver is not None:
+                if ver[0] != t[1]:
+                    return False
+                seen = True
         return seen
 
     def rekey(self, key):
-        if not isinstance(key, tuple):
-            return key
-        out = list(key)
-        for i, x in enumerate(key):
-            if type(x) is int and i + 1 < len(key) and type(key[i + 1]) is int and x in self.vmap and self.vmap[x][0] == key[i + 1]:
-                out[i + 1] = self.vmap[x][1]
-            elif isinstance(x, tuple):
-                out[i] = self.rekey(x)
-        return tuple(out)
+        """`key` with every written tensor it names at its pre-update version moved to the new one."""
+        def moved(t):
+            ver = None if t is None else self.vmap.get(t[0])
+            return (t[0], ver[1]) if ver is not None and ver[0] == t[1] else t
+        return key._replace(tensors=tuple(moved(t) for t in key.tensors))
+
+    def each(self, cache):
+        """(entry, drop) of every current entry of one holder's cache; drop() takes the entry out of the cache."""
+        def dropper(slot, e):
+            def drop():
+                cache[slot] = [q for q in cache.get(slot, ()) if q is not e]
+            return drop
+        for slot, lst in list(cache.items()):
+            for e in list(lst):
+                if self.current(e.key):
+                    yield e, dropper(slot, e)
 
     def write(self, t, fn):
         old = t._version

@@ -14,10 +14,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _ffi
+from . import _ffi, wcache
 import os
 
-from .conv import (_CACHE_LOCK, conv2d, conv2d_fused, conv2d_fused_pair, conv2d_pair, conv2d_stats, fused_eligible,
+from .conv import (conv2d, conv2d_fused, conv2d_fused_pair, conv2d_pair, conv2d_stats, fused_eligible,
                    pair_eligible, stats_eligible)
 
 #: DKT_FUSE_ENCODER=0: separate normalise / residual-join passes around the encoders' convolutions (A/B switch)
@@ -66,10 +66,6 @@ class _Folded:
     argument of conv.conv2d)."""
 
 
-def _tensor_key(t):
-    return None if t is None else (t.data_ptr(), t._version)
-
-
 def _fold(conv, bn):
     with torch.no_grad():
         g = torch.rsqrt(bn.running_var.double() + bn.eps)
@@ -82,12 +78,30 @@ def _fold(conv, bn):
         return (conv.weight.double() * g.view(-1, 1, 1, 1)).float().contiguous(), b.float().contiguous()
 
 
+def _folded(conv, bn):
+    """conv followed by bn (running statistics):  bn(conv(x)) = conv'(x) with
+    w' = w * g, b' = (b - mean) * g + beta, g = gamma / sqrt(var + eps)  (per output channel).
+    Cached on the conv module; rebuilt when any of the tensors is replaced or written."""
+    def build(key):
+        f = _Folded()
+        f.weight, f.bias = _fold(conv, bn)
+        f.padding = conv.padding
+        f.stride = conv.stride
+        f.dilation = conv.dilation        # conv2d sends dilated / grouped layers to the vendor library
+        f.groups = conv.groups
+        f.key = key
+        f.bn = weakref.ref(bn)            # (for ema.ema_update_; weak: the cache must not tie the modules into a cycle)
+        return f
+    key = wcache.key_of(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    return wcache.cached(conv, "_dkt_folded", str(conv.weight.device), key, build)
+
+
 def _refresh_folded(conv, cache, R):
     """ema.ema_update_: the folded weights and bias rewritten in place (same fold, same buffers); returns the folded layers."""
     out = []
-    for slot, f in list(cache.items()):
+    for f, _ in R.each(cache):
         bn = f.bn()
-        if bn is not None and R.current(f.key):
+        if bn is not None:
             w, b = _fold(conv, bn)
             R.write(f.weight, lambda: f.weight.copy_(w))
             R.write(f.bias, lambda: f.bias.copy_(b))
@@ -96,46 +110,7 @@ def _refresh_folded(conv, cache, R):
     return out
 
 
-def _refresh_merged(layer, cache, R):
-    """ema.ema_update_: the side-by-side heads (_merged_outputs) rewritten in place; returns the merged layers."""
-    out = []
-    for slot, m in list(cache.items()):
-        layers = [r() for r in m.layers]
-        if all(l is not None for l in layers) and R.current(m.key):
-            R.write(m.weight, lambda: torch.cat([l.weight.detach().float() for l in layers], 0, out=m.weight))
-            R.write(m.bias, lambda: torch.cat([(l.bias.detach().float() if l.bias is not None else
-                                                torch.zeros(l.weight.shape[0], device=l.weight.device)) for l in layers], 0,
-                                               out=m.bias))
-            m.key = R.rekey(m.key)
-            out.append(m)
-    return out
-
-
-def _folded(conv, bn):
-    """conv followed by bn (running statistics):  bn(conv(x)) = conv'(x) with
-    w' = w * g, b' = (b - mean) * g + beta, g = gamma / sqrt(var + eps)  (per output channel).
-    Cached on the conv module; rebuilt when any of the tensors is replaced or written."""
-    with _CACHE_LOCK:
-        return _folded_locked(conv, bn)
-
-
-def _folded_locked(conv, bn):
-    key = tuple(_tensor_key(t) for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var))
-    cache = conv.__dict__.setdefault("_dkt_folded", {})      # per device: replicas share this dict
-    slot = str(conv.weight.device)
-    hit = cache.get(slot)
-    if hit is not None and hit.key == key:
-        return hit
-    f = _Folded()
-    f.weight, f.bias = _fold(conv, bn)
-    f.padding = conv.padding
-    f.stride = conv.stride
-    f.dilation = conv.dilation        # conv2d sends dilated / grouped layers to the vendor library
-    f.groups = conv.groups
-    f.key = key
-    f.bn = weakref.ref(bn)            # (for ema.ema_update_; weak: the cache must not tie the modules into a cycle)
-    cache[slot] = f
-    return f
+wcache.register("_dkt_folded", _refresh_folded, derived=True)
 
 
 def _foldable(conv, norm, x):
@@ -355,25 +330,43 @@ def _init_like_reference(module):
 PAIR_HEADS = True
 
 
+def _merged_weight(layers, out=None):
+    return torch.cat([l.weight.detach().float() for l in layers], 0, out=out)
+
+
+def _merged_bias(layers, out=None):
+    return torch.cat([(l.bias.detach().float() if l.bias is not None else
+                       torch.zeros(l.weight.shape[0], device=l.weight.device)) for l in layers], 0, out=out)
+
+
 def _merged_outputs(layers):
     """One layer computing the outputs of `layers` (same input, same filter geometry) side by side; cached on the first."""
-    with _CACHE_LOCK:
-        key = tuple(_tensor_key(t) for l in layers for t in (l.weight, l.bias))
-        cache = layers[0].__dict__.setdefault("_dkt_merged", {})
-        slot = str(layers[0].weight.device)
-        hit = cache.get(slot)
-        if hit is not None and hit.key == key:
-            return hit
+    def build(key):
         m = _Folded()
         with torch.no_grad():
-            m.weight = torch.cat([l.weight.detach().float() for l in layers], 0).contiguous()
-            m.bias = torch.cat([(l.bias.detach().float() if l.bias is not None else
-                                 torch.zeros(l.weight.shape[0], device=l.weight.device)) for l in layers], 0).contiguous()
+            m.weight, m.bias = _merged_weight(layers).contiguous(), _merged_bias(layers).contiguous()
         m.padding, m.stride, m.dilation, m.groups = layers[0].padding, layers[0].stride, layers[0].dilation, layers[0].groups
         m.key = key
         m.layers = [weakref.ref(l) for l in layers]      # (for ema.ema_update_; weak: no cycle through layers[0]'s cache)
-        cache[slot] = m
         return m
+    key = wcache.key_of(*[t for l in layers for t in (l.weight, l.bias)])
+    return wcache.cached(layers[0], "_dkt_merged", str(layers[0].weight.device), key, build)
+
+
+def _refresh_merged(layer, cache, R):
+    """ema.ema_update_: the side-by-side heads (_merged_outputs) rewritten in place; returns the merged layers."""
+    out = []
+    for m, _ in R.each(cache):
+        layers = [r() for r in m.layers]
+        if all(l is not None for l in layers):
+            R.write(m.weight, lambda: _merged_weight(layers, m.weight))
+            R.write(m.bias, lambda: _merged_bias(layers, m.bias))
+            m.key = R.rekey(m.key)
+            out.append(m)
+    return out
+
+
+wcache.register("_dkt_merged", _refresh_merged, derived=True)
 
 
 def _same_geometry(a, b):
@@ -458,13 +451,8 @@ class _Trunk(nn.Module):
         B, _, H, W = x.shape
         if torch.cuda.is_current_stream_capturing():
             return c8.ActC8(B, 64, H, W, x.device), c8.ActC8(B, 64, H, W, x.device)
-        key = (B, H, W, str(x.device))
-        with _CACHE_LOCK:
-            cache = self.__dict__.setdefault("_dkt_c8_buf", {})
-            hit = cache.get(str(x.device))
-            if hit is None or hit[0] != key:
-                hit = cache[str(x.device)] = (key, c8.ActC8(B, 64, H, W, x.device), c8.ActC8(B, 64, H, W, x.device))
-        return hit[1], hit[2]
+        new = lambda key: wcache.Entry(key, (c8.ActC8(B, 64, H, W, x.device), c8.ActC8(B, 64, H, W, x.device)))
+        return wcache.cached(self, "_dkt_c8_buf", str(x.device), wcache.Key((), (B, H, W)), new).value
 
     def _layer1_c8(self, x, kind):
         """conv1 / norm1 / relu + layer1 (core/extractor.py:140-146, :167-173 with ResidualBlock :52-60) on conv_c8: every
@@ -515,6 +503,9 @@ class _Trunk(nn.Module):
         """`begun`: the result of _trunk_begin(x) when the caller has enqueued that stage already (RAFTStereo._encode puts the
         context encoder's full-resolution stage on the device BEFORE it enqueues the feature encoder on the second stream)."""
         return self.layer3(self.layer2(self._trunk_begin(x) if begun is None else begun))
+
+
+wcache.register("_dkt_c8_buf", weights=False)      # (_Trunk._c8_buffers: activations, no weights)
 
 
 class BasicEncoder(_Trunk):

@@ -17,7 +17,7 @@ dkt_corr1d_pool_bwd; ``disp`` must be detached, as the reference's loop does.
 import torch
 
 from . import _ffi
-from .corr import _BuildFn, _WT_LOCK, _build_pyramid
+from .corr import _BuildFn, _build_pyramid, _kmajor_weight
 
 
 def _pool_geo(geo_volume, num_levels, out=None):
@@ -190,13 +190,7 @@ class Combined_Geo_Encoding_Volume:
             disp = disp.float().contiguous()
         coords = coords.float().contiguous()
         cout = w.shape[0]
-        key = (w.data_ptr(), w._version)
-        with _WT_LOCK:
-            cache = layer.__dict__.setdefault("_dkt_wt", {})
-            hit = cache.get(str(w.device))
-            if hit is None or hit[0] != key:
-                hit = cache[str(w.device)] = (key, w.detach().reshape(cout, -1).t().float().contiguous())
-        wm = hit[1]
+        wm = _kmajor_weight(layer)
         bias = layer.bias
         out = None if out_c8 is not None else torch.empty((b, cout, h, wd), device=disp.device, dtype=torch.float32)
         tp = torch.empty((b, w.shape[1], h, wd), device=disp.device, dtype=torch.float32) if tap else None

@@ -20,6 +20,7 @@ import weakref
 import torch
 
 from . import conv as _conv
+from . import wcache
 from . import conv_c8 as c8
 from . import loop_c8
 from .conv import conv2d
@@ -193,14 +194,12 @@ def _iterate_rotated(ub, st, iters):
 def _fingerprint(update_block):
     """Everything a captured iteration holds pointers to through a cached derivative (packed weight
     images, merged z|r weights, biases): a changed parameter or backend must force a new capture."""
-    fp = [(_conv.get_backend(), FUSE_GATES)]
-    for t in update_block.parameters():
-        fp.append((t.data_ptr(), t._version))
+    extra = [(_conv.get_backend(), FUSE_GATES)]
     for m in update_block.modules():
         e = getattr(m, "dkt_in_exp", None)       # calibrated activation exponents are baked into the captured launches
         if e:
-            fp.append(("in_exp", id(m), e))
-    return tuple(fp)
+            extra.append(("in_exp", id(m), e))
+    return wcache.key_of(*update_block.parameters(), extra=tuple(extra))
 
 
 #: a replica made by nn.DataParallel hands its loop to a persistent per-device copy of the master's update block
@@ -230,7 +229,7 @@ class _ShadowBlock:
 
     def _sync(self, master):
         src = self._tensors(master)
-        fp = tuple((t.data_ptr(), t._version) for t in src)
+        fp = wcache.key_of(*src)
         if self.block is None:
             grus = [m for m in (getattr(master, n, None) for n in ("gru16", "gru08", "gru04")) if m is not None]
             hidden = [int(g.convz.weight.shape[0]) for g in grus]

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _ffi
+from . import _ffi, wcache
 from .conv import conv2d
 from .corr import CORR_IMPLEMENTATIONS
 from .extractor import BasicEncoder, MultiBasicEncoder, ResidualBlock
@@ -110,7 +110,7 @@ class _Shadow:
 
     def _sync(self, master):
         src = self._tensors(master)
-        fp = tuple((t.data_ptr(), t._version) for t in src)
+        fp = wcache.key_of(*src)
         if self.model is None:
             self.model = type(master)(master.args).to(self.device)
             self.model._is_shadow = True
@@ -255,17 +255,16 @@ class RAFTStereo(nn.Module):
     graph_encoders = os.environ.get("DKT_GRAPH_ENCODERS", "0") == "1"
 
     def _encoder_fingerprint(self):
-        fp = [(_conv.get_backend(), _extractor.FUSE_ENCODER, self.encoder_streams)]
+        tensors, extra = [], [(_conv.get_backend(), _extractor.FUSE_ENCODER, self.encoder_streams)]
         for mod in ([self.fnet] if self._two_encoders else [m for m in [getattr(self, "conv2", None)] if m is not None]) + [self.cnet, self.context_zqr_convs]:
-            for t in list(mod.parameters()) + list(mod.buffers()):
-                fp.append((t.data_ptr(), t._version))
+            tensors += list(mod.parameters()) + list(mod.buffers())
             for m in mod.modules():
                 e = getattr(m, "dkt_in_exp", None)
                 if e:
-                    fp.append(("in_exp", id(m), e))
+                    extra.append(("in_exp", id(m), e))
                 if isinstance(m, nn.BatchNorm2d):
-                    fp.append(("bn", id(m), m.training))
-        return tuple(fp)
+                    extra.append(("bn", id(m), m.training))
+        return wcache.key_of(*tensors, extra=tuple(extra))
 
     @property
     def _mixed(self):
@@ -295,8 +294,9 @@ class RAFTStereo(nn.Module):
 
     def _encode_graphed(self, image1, image2):
         target = self._prebuild_target(image1)
-        key = (image1.device, tuple(image1.shape), self.args.n_gru_layers, self._encoder_fingerprint(),
-               None if target is None else (id(target), tuple(p.data_ptr() for p in target.corr_pyramid)))
+        fp = self._encoder_fingerprint()
+        key = fp._replace(extra=(image1.device, tuple(image1.shape), self.args.n_gru_layers, fp.extra,
+                                 None if target is None else (id(target), tuple(p.data_ptr() for p in target.corr_pyramid))))
         tid = threading.get_ident()
         with _GRAPH_LOCK:
             st = _ENCODER_STATES.setdefault(self, {}).get(tid)
@@ -547,15 +547,13 @@ class RAFTStereo(nn.Module):
                 and self.update_block.side_stream)
 
     def _weights_fingerprint(self):
-        """(data_ptr, version) of every tensor the captured iteration reads through a cached derivative."""
-        fp = [(_conv.get_backend(), FUSE_GATES)]
-        for t in self.update_block.parameters():
-            fp.append((t.data_ptr(), t._version))
+        """The wcache.Key of every tensor the captured iteration reads through a cached derivative."""
+        extra = [(_conv.get_backend(), FUSE_GATES)]
         for m in self.update_block.modules():
             e = getattr(m, "dkt_in_exp", None)
             if e:
-                fp.append(("in_exp", id(m), e))
-        return tuple(fp)
+                extra.append(("in_exp", id(m), e))
+        return wcache.key_of(*self.update_block.parameters(), extra=tuple(extra))
 
     def _ema_rekey(self, R):
         """ema.ema_update_ has rewritten every weight derivative of this model in place: the captured loop and encoder
@@ -566,7 +564,7 @@ class RAFTStereo(nn.Module):
             for states in (_GRAPH_STATES.get(self, {}), _ENCODER_STATES.get(self, {})):
                 for st in states.values():
                     lp = st.get("c8")
-                    if lp is not None and any(R.current(getattr(p, "key", None)) for p in lp.pinned):
+                    if lp is not None and any(R.current(p.key) for p in lp.pinned):
                         continue
                     if R.current(st["key"]):
                         st["key"] = R.rekey(st["key"])
@@ -790,8 +788,9 @@ class RAFTStereo(nn.Module):
         # The captured graph bakes in device pointers to the packed weight images, the merged z|r
         # weights and the biases, all of which are re-created when a parameter is replaced or written
         # (load_state_dict, .to(), optimiser steps) or the conv backend changes: those are part of the key.
-        key = (fmap1.device, tuple(fmap1.shape), tuple(fmap2.shape), args.corr_implementation,
-               self._weights_fingerprint(), self.rotate, self.pair_grus, self.pipeline_grus, self.fuse_lookup, self.use_c8)
+        fp = self._weights_fingerprint()
+        key = fp._replace(extra=(fmap1.device, tuple(fmap1.shape), tuple(fmap2.shape), args.corr_implementation, fp.extra,
+                                 self.rotate, self.pair_grus, self.pipeline_grus, self.fuse_lookup, self.use_c8))
         st = self._graph_state
         prebuilt, self._prebuilt = self._prebuilt, None
         static, self._static_ctx = self._static_ctx, None

@@ -32,9 +32,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _ffi, gru_train
+from . import _ffi, gru_train, wcache
 from . import conv as _conv
-from .conv import (_CACHE_LOCK, conv2d, conv2d_accumulate, conv2d_gate_out, conv2d_gate_out_pair, conv2d_gate_zr,
+from .conv import (conv2d, conv2d_accumulate, conv2d_gate_out, conv2d_gate_out_pair, conv2d_gate_zr,
                    conv2d_autograd, conv2d_gate_zr_pair, conv2d_pair, few_eligible, get_backend, hip_eligible, pair_eligible)
 
 
@@ -190,14 +190,13 @@ class FlowHead(nn.Module):
 class _LayerView:
     """The first n output channels of a convolution layer (duck-types the `layer` argument of conv.conv2d)."""
 
-    def __init__(self, layer, n):
+    def __init__(self, layer, n, key):
         self._parent = layer
+        self.n, self.key = n, key
         self.weight = layer.weight[:n]
         self.bias = None if layer.bias is None else layer.bias[:n]
         self.padding, self.stride, self.dilation, self.groups = layer.padding, layer.stride, layer.dilation, layer.groups
         self.padding_mode = layer.padding_mode
-        self._key = (layer.weight.data_ptr(), layer.weight._version,
-                     None if layer.bias is None else (layer.bias.data_ptr(), layer.bias._version), n)
 
     @property
     def dkt_in_exp(self):                      # the activation exponent (conv.calibrate) lives on the real layer
@@ -212,47 +211,44 @@ class _ScaledLayer(_LayerView):
     """`layer` with weight and bias multiplied by a power of two: scale * layer(x) in the layer's own launch (exact in fp32,
     so bit-identical to scaling the result -- the reference's `.25 * self.mask(net)`, core/update.py:136)."""
 
-    def __init__(self, layer, scale):
-        super().__init__(layer, layer.weight.shape[0])
+    def __init__(self, layer, scale, key):
+        super().__init__(layer, layer.weight.shape[0], key)
+        self.scale = scale
         with torch.no_grad():
             self.weight = (layer.weight.detach() * scale).contiguous()
             self.bias = None if layer.bias is None else (layer.bias.detach() * scale).contiguous()
-        self._key = self._key[:3] + (("scale", scale),)
 
 
 def _scaled_layer(layer, scale):
     m, e = math.frexp(scale)
     if m != 0.5:
         raise ValueError("_scaled_layer: %r is not a power of two" % (scale,))
-    key = (layer.weight.data_ptr(), layer.weight._version,
-           None if layer.bias is None else (layer.bias.data_ptr(), layer.bias._version), ("scale", scale))
-    view = layer.__dict__.get("_dkt_scaled")
-    if view is None or view._key != key:
-        view = layer.__dict__["_dkt_scaled"] = _ScaledLayer(layer, scale)
-    return view
+    return wcache.cached(layer, "_dkt_scaled", str(layer.weight.device),
+                         wcache.key_of(layer.weight, layer.bias, extra=(("scale", scale),)),
+                         lambda key: _ScaledLayer(layer, scale, key))
 
 
 def _leading_outputs(layer, n):
-    key = (layer.weight.data_ptr(), layer.weight._version,
-           None if layer.bias is None else (layer.bias.data_ptr(), layer.bias._version), n)
-    view = layer.__dict__.get("_dkt_view")
-    if view is None or view._key != key:
-        view = layer.__dict__["_dkt_view"] = _LayerView(layer, n)
-    return view
+    return wcache.cached(layer, "_dkt_view", str(layer.weight.device), wcache.key_of(layer.weight, layer.bias, extra=(n,)),
+                         lambda key: _LayerView(layer, n, key))
 
 
-def _refresh_view(layer, view, R):
+def _refresh_view(layer, cache, R):
     """ema.ema_update_: a _LayerView's tensors are views of the layer's own (already updated): only its key moves.  A
-    _ScaledLayer's copies are rewritten in place.  Returns the view (its own caches are refreshed next)."""
-    if not R.current(view._key):
-        return None
-    if isinstance(view, _ScaledLayer):
-        scale = view._key[3][1]
-        R.write(view.weight, lambda: torch.mul(layer.weight.detach(), scale, out=view.weight))
-        if view.bias is not None:
-            R.write(view.bias, lambda: torch.mul(layer.bias.detach(), scale, out=view.bias))
-    view._key = R.rekey(view._key)
-    return view
+    _ScaledLayer's copies are rewritten in place.  Returns the views (their own caches are refreshed next)."""
+    out = []
+    for view, _ in R.each(cache):
+        if isinstance(view, _ScaledLayer):
+            R.write(view.weight, lambda: torch.mul(layer.weight.detach(), view.scale, out=view.weight))
+            if view.bias is not None:
+                R.write(view.bias, lambda: torch.mul(layer.bias.detach(), view.scale, out=view.bias))
+        view.key = R.rekey(view.key)
+        out.append(view)
+    return out
+
+
+wcache.register("_dkt_view", _refresh_view, derived=True)
+wcache.register("_dkt_scaled", _refresh_view, derived=True)
 
 
 class DispHead(FlowHead):
@@ -290,35 +286,29 @@ class ConvGRU(nn.Module):
         self.convz = nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel_size, padding=pad)
         self.convr = nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel_size, padding=pad)
         self.convq = nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel_size, padding=pad)
-        self._zr_cache = None        # {device: (key, merged layer)}; shared by replicate()'s shallow copies
+        self._zr_cache = None        # a wcache cache of _MergedZR layers; shared by replicate()'s shallow copies
 
     def _merged_zr(self):
         """convz | convr as one Conv2d-like (weight, bias) pair per device, rebuilt whenever
         either parameter tensor is replaced or written (load_state_dict, .to())."""
         wz, wr = self.convz.weight, self.convr.weight
         bz, br = self.convz.bias, self.convr.bias
-        key = tuple((t.data_ptr(), t._version) for t in (wz, wr, bz, br))
-        with _CACHE_LOCK:
-            cache = self._zr_cache
-            if cache is None:
-                cache = self._zr_cache = {}
-            hit = cache.get(str(wz.device))
-            if hit is None or hit[0] != key:
-                with torch.no_grad():
-                    zr = _MergedZR(self.convz, torch.cat([wz, wr], dim=0).contiguous(),
-                                   torch.cat([self.convz.bias, self.convr.bias], dim=0).contiguous())
-                hit = cache[str(wz.device)] = (key, zr)
-            return hit[1]
+
+        def build(key):
+            with torch.no_grad():
+                zr = _MergedZR(self.convz, torch.cat([wz, wr], dim=0).contiguous(), torch.cat([bz, br], dim=0).contiguous())
+            zr.key = key
+            return zr
+        return wcache.cached(self, "_zr_cache", str(wz.device), wcache.key_of(wz, wr, bz, br), build)
 
     def _refresh_zr(self, cache, R):
         """ema.ema_update_: the merged z|r layer rewritten in place; returns the merged layers (their caches come next)."""
         out = []
-        for dev, (key, zr) in list(cache.items()):
-            if R.current(key):
-                R.write(zr.weight, lambda: torch.cat([self.convz.weight.detach(), self.convr.weight.detach()], dim=0, out=zr.weight))
-                R.write(zr.bias, lambda: torch.cat([self.convz.bias.detach(), self.convr.bias.detach()], dim=0, out=zr.bias))
-                cache[dev] = (R.rekey(key), zr)
-                out.append(zr)
+        for zr, _ in R.each(cache):
+            R.write(zr.weight, lambda: torch.cat([self.convz.weight.detach(), self.convr.weight.detach()], dim=0, out=zr.weight))
+            R.write(zr.bias, lambda: torch.cat([self.convz.bias.detach(), self.convr.bias.detach()], dim=0, out=zr.bias))
+            zr.key = R.rekey(zr.key)
+            out.append(zr)
         return out
 
     def forward(self, h, cz, cr, cq, *x_list, out=None):
@@ -366,6 +356,9 @@ class ConvGRU(nn.Module):
                                 B, Ch, HW, dev, st)
         _ffi.check(rc, "dkt_gru_gate_out")
         return out
+
+
+wcache.register("_zr_cache", ConvGRU._refresh_zr, derived=True)
 
 
 def gru_pair(gru_a, args_a, gru_b, args_b):

@@ -160,6 +160,30 @@ def test_conv_weight_cache_invalidation():
     assert not torch.equal(a, b)
 
 
+@torch.no_grad()
+def test_clear_weight_cache_after_data_write():
+    """A write through `.data` leaves the version counter alone, so every cached image stays "current":
+    conv.clear_weight_cache() is what makes the next call repack.  Doubling the weights (bias zeroed) must double the result
+    bit for bit, on the split-fp16 kernel and on the C8S kernel.  The C8S half fails before clear_weight_cache went over
+    wcache's registry: it left `_dkt_packed_c8` in place and the second call ran the old image."""
+    from dkt_stereo_amd import conv, conv_c8
+    conv.set_backend("f16x3")
+    layer = torch.nn.Conv2d(16, 64, 3, padding=1).to(DEV)
+    layer.bias.zero_()
+    x = G(_synth.normal((1, 16, 8, 32), 92, "x"))
+    runs = {"conv2d": lambda: conv.conv2d(x, layer), "conv2d_c8": lambda: conv_c8.conv2d_c8([conv_c8.pack(x)], layer)}
+    first = {k: f() for k, f in runs.items()}
+    layer.weight.data.mul_(2.0)
+    conv.clear_weight_cache(layer)
+    ref = F.conv2d(x.double(), layer.weight.double(), None, padding=1)
+    for k, f in runs.items():
+        y = f()
+        err = float((y.double() - ref).abs().max()) / float(ref.abs().max())
+        print("%s after .data.mul_(2) + clear_weight_cache: rel err vs fp64 %.3g" % (k, err))
+        assert torch.equal(y, 2.0 * first[k]), k
+        assert err <= 2e-6, k
+
+
 @pytest.mark.parametrize("name", list(_cases.UPDATE_CASES))
 @torch.no_grad()
 def test_update_block_f16x3(name, golden):

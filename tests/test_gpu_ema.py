@@ -74,14 +74,13 @@ def _holders(model):
         seen.add(id(h))
         out.append(h)
         d = h.__dict__
-        todo += list(d.get("_dkt_folded", {}).values()) + list(d.get("_dkt_merged", {}).values())
-        todo += [zr for _, zr in (d.get("_zr_cache") or {}).values()]
-        todo += [v for v in (d.get("_dkt_view"), d.get("_dkt_scaled")) if v is not None]
+        for name in ("_dkt_folded", "_dkt_merged", "_zr_cache", "_dkt_view", "_dkt_scaled"):
+            todo += [e for lst in (d.get(name) or {}).values() for e in lst]
     return out
 
 
 def _current(key, w):
-    return key[0] == w.data_ptr() and key[1] == w._version
+    return key.tensors[0] == (w.data_ptr(), w._version)
 
 
 def _check_packs_cold_equal(model):
@@ -98,27 +97,27 @@ def _check_packs_cold_equal(model):
                 if not _current(p.key, w):
                     continue
                 wc = w.detach().float()
-                if p.key[4] is not None:
-                    wc = wc * c8._in_scale_vector(p.key[4], w.device).view(1, -1, 1, 1)
+                if p.scales is not None:
+                    wc = wc * c8._in_scale_vector(p.scales, w.device).view(1, -1, 1, 1)
                 img = torch.zeros_like(p.img)
-                c8._repack_raw(wc, p.key[3], p.inv_scale, img)
+                c8._repack_raw(wc, p.src_channels, p.inv_scale, img)
                 assert torch.equal(img, p.img)
                 n += 1
         for lst in h.__dict__.get("_dkt_gru_c8", {}).values():
             for p in lst:
-                if p.key[0] != (h.convz.weight.data_ptr(), h.convz.weight._version):
+                if not _current(p.key, h.convz.weight):
                     continue
-                wzr, wq2, ch = c8._gru_images(h, *p.key[6:9])
+                wzr, wq2, ch = c8._gru_images(h, p.x_channels, p.hs, p.xs)
                 a, b = torch.zeros_like(p.wzr), torch.zeros_like(p.wq)
-                c8._repack_raw(wzr, [ch] + list(p.key[6]), p.inv_zr, a)
-                c8._repack_raw(wq2, list(p.key[6]) + [ch], p.inv_q, b)
+                c8._repack_raw(wzr, [ch] + list(p.x_channels), p.inv_zr, a)
+                c8._repack_raw(wq2, list(p.x_channels) + [ch], p.inv_q, b)
                 assert torch.equal(a, p.wzr) and torch.equal(b, p.wq)
                 assert torch.equal(p.bz, h.convz.bias) and torch.equal(p.bq, h.convq.bias)
                 n += 1
-        for p in h.__dict__.get("_dkt_packed", {}).values():
+        for p in (p for lst in h.__dict__.get("_dkt_packed", {}).values() for p in lst):
             if not _current(p.key, w):
                 continue
-            chs = p.key[3]
+            chs = p.src_channels
             ch = (ctypes.c_int * len(chs))(*chs)
             hi, lo = torch.empty_like(p.hi), torch.empty_like(p.lo)
             wc = w.detach().float().contiguous()
@@ -129,15 +128,15 @@ def _check_packs_cold_equal(model):
             if p.bias is not None:
                 assert torch.equal(p.bias, h.bias.detach().float())
             n += 1
-        for key, t in h.__dict__.get("_dkt_head_w", {}).values():
-            if _current(key, w):
-                assert torch.equal(t[:, :, :9], w.detach().float().reshape(w.shape[0], w.shape[1], 9))
+        for e in (e for lst in h.__dict__.get("_dkt_head_w", {}).values() for e in lst):
+            if _current(e.key, w):
+                assert torch.equal(e.value[:, :, :9], w.detach().float().reshape(w.shape[0], w.shape[1], 9))
                 n += 1
-        for key, wm in h.__dict__.get("_dkt_wt", {}).values():
-            if _current(key, w):
-                assert torch.equal(wm, w.detach().reshape(w.shape[0], -1).t())
+        for e in (e for lst in h.__dict__.get("_dkt_wt", {}).values() for e in lst):
+            if _current(e.key, w):
+                assert torch.equal(e.value, w.detach().reshape(w.shape[0], -1).t())
                 n += 1
-        for pk in h.__dict__.get("_dkt_stem7", {}).values():
+        for pk in (p for lst in h.__dict__.get("_dkt_stem7", {}).values() for p in lst):
             if not _current(pk.key, w):
                 continue
             hi, lo = torch.empty_like(pk.hi), torch.empty_like(pk.lo)
@@ -243,10 +242,10 @@ def test_window_exit_goes_cold():
     assert not info["warm"]
     for h in _holders(teacher.update_block):                 # every pack of the scaled layers was dropped, none is current
         for name in ("_dkt_packed_c8", "_dkt_packed", "_dkt_stem7"):
-            for v in h.__dict__.get(name, {}).values():
-                assert not any(_current(p.key, h.weight) for p in (v if isinstance(v, list) else [v])), name
+            for lst in h.__dict__.get(name, {}).values():
+                assert not any(_current(p.key, h.weight) for p in lst), name
         for lst in h.__dict__.get("_dkt_gru_c8", {}).values():
-            assert not any(p.key[0] == (h.convz.weight.data_ptr(), h.convz.weight._version) for p in lst)
+            assert not any(_current(p.key, h.convz.weight) for p in lst)
     _, got = teacher(*pair, iters=ITERS, test_mode=True)
     assert teacher._graph_state is not st
     _, want = _fresh_like(teacher)(*pair, iters=ITERS, test_mode=True)
