@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _ffi, wcache
+from . import _ffi, norm_train, wcache
 import os
 
 from .conv import (conv2d, conv2d_fused, conv2d_fused_pair, conv2d_pair, conv2d_stats, fused_eligible,
@@ -40,13 +40,27 @@ C8_ENCODER_MIN_PIXELS = 100000
 C8_ENCODER_CFG = 3
 
 
+#: the affine-free instance norms and residual joins of an encoder under autograd (fnet in training) as the HIP autograd
+#: nodes of norm_train.py instead of torch's InstanceNorm2d / relu / add sequence (A/B handle).  Off until
+#: tools/bench_encoder_train.py has shown arm b ahead of arm a by more than the a-to-a spread at both training shapes:
+#: not measured yet (DESIGN 3.15 holds the numbers that exist).
+TRAIN_NORM_NODES = False
+
+
 def _hip_ok(x):
     return x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)
 
 
+def _hip_f32(x):
+    return torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+
+
 def norm_act(norm, x, relu):
     """norm(x) [+ ReLU].  InstanceNorm2d (affine-free, instance statistics: fnet) runs as the
-    fused dkt_instance_norm; every other norm is torch (+ F.relu)."""
+    fused dkt_instance_norm -- under autograd as its node, norm_train.instance_norm --; every other norm is torch
+    (+ F.relu)."""
+    if (TRAIN_NORM_NODES and _plain_instance_norm(norm) and _hip_f32(x) and torch.is_grad_enabled() and x.requires_grad):
+        return norm_train.instance_norm(x, norm.eps, relu)
     if (isinstance(norm, nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats and _hip_ok(x)):
         x = x.contiguous()
         n, c, h, w = x.shape
@@ -160,6 +174,9 @@ def norm_add_relu(norm, x, c, c_stats=None):
     lazy = x if isinstance(x, LazyNorm) else None
     if lazy is not None:
         x = lazy.raw
+    if (TRAIN_NORM_NODES and lazy is None and _plain_instance_norm(norm) and _hip_f32(x) and _hip_f32(c)
+            and torch.is_grad_enabled() and (x.requires_grad or c.requires_grad) and x.shape == c.shape):
+        return norm_train.instance_norm_add_relu(x, c, norm.eps)       # (under autograd: the join as one node)
     if _plain_instance_norm(norm) and _hip_ok(x) and _hip_ok(c) and x.shape == c.shape:
         x = x.contiguous()
         c = c.contiguous()

@@ -569,6 +569,24 @@ int dkt_instance_norm_add_relu_lazy(const float *a, const float *a_mean_invstd /
 int dkt_instance_norm_finalize(const void *workspace, int planes, long HW, float eps, float *mean_invstd /* (planes,2) */,
                                int device, void *stream);
 
+/* Their gradients on the training path (torch autograd through core/extractor.py:21-33 with norm_fn='instance' -- the
+ * batch-norm backward behind F.instance_norm plus the threshold backward of the ReLU -- and through the tail of a
+ * residual block, core/extractor.py:52-60: two threshold backwards, the add and the norm's backward).  `planes`
+ * contiguous planes of HW floats; mean_invstd (planes,2) from dkt_instance_norm_finalize on the forward's workspace.
+ * yh = (x - mean) * invstd is recomputed (the forward's own pre-ReLU bits), g is the masked upstream gradient:
+ *   dkt_instance_norm_bwd:           g = gy * [yh > 0] (relu) or gy;     gx = invstd * (g - mean(g) - yh * mean(g * yh))
+ *   dkt_instance_norm_add_relu_bwd:  ga = gout * [out > 0];  g = ga * [yh_c > 0];  gc as gx above, from c
+ * The plane sums are fp64, taken by several blocks per plane into `workspace` (dkt_instance_norm_bwd_workspace() bytes,
+ * device memory) and added in slice order: no atomics, bit-identical from run to run.  Two launches; ga or gc may be
+ * NULL (not both), and with gc == NULL no sums are taken, one launch runs and c, mean_invstd and workspace are not read.
+ * Errors: null pointer DKT_E_NULL; planes <= 0, HW <= 0 or planes > 65535 DKT_E_SHAPE. */
+long dkt_instance_norm_bwd_workspace(int planes, long HW);
+int dkt_instance_norm_bwd(const float *gy, const float *x, const float *mean_invstd /* (planes,2) */, int relu, float *gx,
+                          void *workspace, int planes, long HW, int device, void *stream);
+int dkt_instance_norm_add_relu_bwd(const float *gout, const float *out, const float *c,
+                                   const float *mean_invstd /* (planes,2) */, float *ga /* nullable */,
+                                   float *gc /* nullable */, void *workspace, int planes, long HW, int device, void *stream);
+
 int dkt_add_relu(const float *a, const float *b, float *y, long n, int device, void *stream);
 
 /* ---- EMA teacher update (csrc/ema.hip) ----------------------------------------------------------------------
