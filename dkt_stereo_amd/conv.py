@@ -678,9 +678,9 @@ GRAD_PREPASS = True
 class _LayerShim:
     """Duck-types the `layer` argument of conv2d() for detached tensors inside the autograd function."""
 
-    def __init__(self, weight, bias, padding):
+    def __init__(self, weight, bias, padding, stride=(1, 1)):
         self.weight, self.bias, self.padding = weight, bias, padding
-        self.stride, self.dilation, self.groups, self.padding_mode = (1, 1), (1, 1), 1, "zeros"
+        self.stride, self.dilation, self.groups, self.padding_mode = stride, (1, 1), 1, "zeros"
 
 
 class _Conv2dFn(torch.autograd.Function):
@@ -816,6 +816,75 @@ def conv2d_wgrad(x, g, scale, k, x_scale=1.0):
     return gw
 
 
+#: stride-2 (Cin, Cout, K) classes whose weight gradient stays on the vendor call with the handle on: rows of
+#: `tools/bench_encoder_train.py --conv` that lost to it (us of dkt_conv2d_wgrad_s2 vs us of the vendor call)
+WGRAD_S2_VENDOR_CLASSES = {}
+#: ... and whose input gradient does (us of dkt_conv2d_dgrad_s2 vs us of torch.nn.grad.conv2d_input)
+DGRAD_S2_VENDOR_CLASSES = {}
+
+
+def _out_size_s2(H, W):
+    return (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+def conv2d_dgrad_s2(g, layer, scale, hw, pack_scale=None, out=None):
+    """dkt_conv2d_dgrad_s2: the (B, Cin, H, W) input gradient of a stride-2, padding k/2, k x k convolution (k in {1, 3}) from
+    the masked gradient `g` (B, Cout, Ho, Wo), fp32 with dense batch elements (a view with a longer batch stride is read in
+    place).  `layer` is the input-gradient layer (_grad_layer(owner): the weight transposed over (Cout, Cin) and rotated by
+    180 degrees, packed once per weight version at `pack_scale`, the forward image's scale), `scale` the device pair
+    conv_grad_prepass left for `g`, `hw` = (H, W) of the forward input, `out` an optional (B, Cin, H, W) fp32 destination
+    with dense batch elements (every element is written).  Nothing is read back on the host."""
+    _ffi.require_gpu(g, scale)
+    B, cout, Ho, Wo = g.shape
+    H, W = int(hw[0]), int(hw[1])
+    cin, wc, k, kw = layer.weight.shape
+    if wc != cout or k != kw or k not in (1, 3):
+        raise ValueError("conv2d_dgrad_s2: g %s does not match the layer %s" % (tuple(g.shape), tuple(layer.weight.shape)))
+    if (Ho, Wo) != _out_size_s2(H, W):
+        raise ValueError("conv2d_dgrad_s2: g %s is not the stride-2 output of a %d x %d input" % (tuple(g.shape), H, W))
+    if not _dense(g) or (B > 1 and g.stride(0) < cout * Ho * Wo):
+        g = g.contiguous()
+    pk = _packed_weights(layer, [cout], pack_scale)
+    if out is None:
+        gx = torch.empty((B, cin, H, W), device=g.device, dtype=torch.float32)
+    elif (not _dense(out) or out.dtype != torch.float32 or tuple(out.shape) != (B, cin, H, W) or out.device != g.device
+          or (B > 1 and out.stride(0) < cin * H * W)):
+        raise ValueError("conv2d_dgrad_s2(out=...) must be a dense-per-batch fp32 tensor of the input's shape")
+    else:
+        gx = out
+    rc = _ffi.lib().dkt_conv2d_dgrad_s2(g.data_ptr(), _batch_stride(g), pk.hi.data_ptr(), pk.lo.data_ptr(), pk.inv_scale,
+                                        scale.data_ptr(), gx.data_ptr(), _batch_stride(gx), B, cin, cout, H, W, k,
+                                        _ffi.device_of(g), _ffi.stream_of(g))
+    _ffi.check(rc, "dkt_conv2d_dgrad_s2")
+    return gx
+
+
+def conv2d_wgrad_s2(x, g, scale, k, x_scale=1.0):
+    """dkt_conv2d_wgrad_s2: the (Cout, Cin, k, k) weight gradient of a stride-2, padding k/2, k x k convolution (k in {1, 3})
+    from its input `x` (B, Cin, H, W) and the masked gradient `g` (B, Cout, Ho, Wo); arguments as conv2d_wgrad."""
+    _ffi.require_gpu(x, g, scale)
+    B, cin, H, W = x.shape
+    cout = g.shape[1]
+    Ho, Wo = _out_size_s2(H, W)
+    if tuple(g.shape) != (B, cout, Ho, Wo):
+        raise ValueError("conv2d_wgrad_s2: g %s is not the stride-2 gradient of x %s" % (tuple(g.shape), tuple(x.shape)))
+    if not _dense(x) or (B > 1 and x.stride(0) < cin * H * W):
+        x = x.contiguous()
+    if not _dense(g) or (B > 1 and g.stride(0) < cout * Ho * Wo):
+        g = g.contiguous()
+    L = _ffi.lib()
+    n = int(L.dkt_conv2d_wgrad_s2_ws_floats(B, cin, cout, H, W, k))
+    if n < 0:
+        _ffi.check(n, "dkt_conv2d_wgrad_s2_ws_floats")
+    gw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32)
+    ws = torch.empty(n, device=x.device, dtype=torch.float32)
+    rc = L.dkt_conv2d_wgrad_s2(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(),
+                               float(x_scale), gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, k, _ffi.device_of(x),
+                               _ffi.stream_of(x))
+    _ffi.check(rc, "dkt_conv2d_wgrad_s2")
+    return gw
+
+
 class _Conv2dGradFn(torch.autograd.Function):
     """conv2d_autograd with GRAD_PREPASS.  apply(x, relu, owner, nparts, *params): `owner` holds the (detached) weight and
     bias the kernels read and every packed image; `params` are the tensors autograd differentiates -- nparts weights, then
@@ -826,6 +895,7 @@ class _Conv2dGradFn(torch.autograd.Function):
         with torch.no_grad():
             y = conv2d(x.detach(), owner, relu=relu)
         ctx.owner, ctx.relu, ctx.nparts, ctx.has_bias = owner, bool(relu), nparts, len(params) > nparts
+        ctx.s2 = _stride_of(owner) == (2, 2)
         ctx.splits = [int(p.shape[0]) for p in params[:nparts]]
         ctx.save_for_backward(x, owner.weight, y if relu else None)
         return y
@@ -842,18 +912,31 @@ class _Conv2dGradFn(torch.autograd.Function):
         with torch.no_grad():
             gy = gy if gy.dtype == torch.float32 else gy.float()
             shim = _grad_layer(ctx.owner) if need_x else None
-            dscale = need_x and _dscale_eligible(shim)
+            cls = (x.shape[1], w.shape[0], kh)
+            if ctx.s2:
+                # stride 2 (k in {1, 3}, _autograd_eligible): dkt_conv2d_dgrad_s2 / dkt_conv2d_wgrad_s2
+                dscale = need_x and get_backend() in _PASSES and cls not in DGRAD_S2_VENDOR_CLASSES
+                vendor_classes = WGRAD_S2_VENDOR_CLASSES
+            else:
+                dscale = need_x and _dscale_eligible(shim)
+                vendor_classes = WGRAD_VENDOR_CLASSES
             wgrad = (need_w and GRAD_WEIGHT_HIP and kh == kw and kh in (1, 3) and x.is_cuda and gy.is_cuda
-                     and x.dtype == torch.float32 and (x.shape[1], w.shape[0], kh) not in WGRAD_VENDOR_CLASSES)
+                     and x.dtype == torch.float32 and cls not in vendor_classes)
             g, scale = gy, None
             if ctx.relu or need_b or dscale or wgrad:
                 g, gb, scale = conv_grad_prepass(gy, y if ctx.relu else None, want_bias=need_b)
-            if need_x:
+            if need_x and ctx.s2:
+                gx = (conv2d_dgrad_s2(g, shim, scale, x.shape[2:], shim.pack_scale) if dscale else
+                      torch.nn.grad.conv2d_input(x.shape, w, g, stride=2, padding=(kh // 2, kw // 2)))
+            elif need_x:
                 gx = conv2d_dscale(g, shim, scale, shim.pack_scale) if dscale else conv2d(g, shim)
-            if wgrad:
+            if wgrad and ctx.s2:
+                gw = conv2d_wgrad_s2(x.detach(), g, scale, kh, 2.0 ** in_exp_of(ctx.owner))
+            elif wgrad:
                 gw = conv2d_wgrad(x.detach(), g, scale, kh, 2.0 ** in_exp_of(ctx.owner))
             elif need_w:
-                gw = torch.nn.grad.conv2d_weight(x.detach(), w.shape, g, stride=1, padding=(kh // 2, kw // 2))
+                gw = torch.nn.grad.conv2d_weight(x.detach(), w.shape, g, stride=2 if ctx.s2 else 1,
+                                                 padding=(kh // 2, kw // 2))
         gws = [None] * n if gw is None else list(gw.split(ctx.splits, 0)) if n > 1 else [gw]
         gbs = [None] * n if gb is None else list(gb.split(ctx.splits, 0)) if n > 1 else [gb]
         gws = [t if ctx.needs_input_grad[4 + i] else None for i, t in enumerate(gws)]
@@ -862,15 +945,20 @@ class _Conv2dGradFn(torch.autograd.Function):
 
 
 def _autograd_eligible(x, layer):
-    """fp32 HIP tensor, stride-1 "same" layer with an odd square kernel, no groups / dilation."""
+    """fp32 HIP tensor, padding k/2, no groups / dilation: a stride-1 layer with an odd square kernel, or a stride-2 layer
+    with k in {1, 3} (the encoders' down-sampling layers; backward on dkt_conv2d_dgrad_s2 / dkt_conv2d_wgrad_s2, which
+    needs the pre-pass: GRAD_PREPASS = False leaves stride 2 to plain torch)."""
     kh, kw = layer.weight.shape[2:]
     pad = _padding_of(layer)
+    st = _stride_of(layer)
     return (x.is_cuda and x.dtype == torch.float32 and kh == kw and kh % 2 == 1 and pad == (kh // 2, kw // 2)
-            and _stride_of(layer) == (1, 1) and _plain_conv(layer))
+            and (st == (1, 1) or (st == (2, 2) and kh in (1, 3) and GRAD_PREPASS and GRAD_WEIGHT_HIP))
+            and _plain_conv(layer))
 
 
 def conv2d_autograd(x, layer, relu=False, owner=None):
-    """[relu](conv(x) + bias) for a stride-1 "same" layer (odd square kernel, no groups / dilation) as an autograd node:
+    """[relu](conv(x) + bias) for a stride-1 "same" layer (odd square kernel, no groups / dilation) or a stride-2 1x1 / 3x3
+    layer with padding k/2 as an autograd node:
     `x` a tensor or a list of tensors (the reference's torch.cat operands).  Other layers run as plain torch.
     `layer` may be a tuple of layers that share input and geometry (ConvGRU's convz, convr): their outputs are
     concatenated along channels, one convolution, and `owner` is then required.
@@ -901,6 +989,6 @@ def conv2d_autograd(x, layer, relu=False, owner=None):
             # a persistent module owns its images; anything else (a namespace around temporaries) packs per call, on an
             # object that dies with the call
             owner = layer if isinstance(layer, torch.nn.Module) else _LayerShim(
-                w.detach(), None if layer.bias is None else layer.bias.detach(), pad)
+                w.detach(), None if layer.bias is None else layer.bias.detach(), pad, _stride_of(layer))
         return _Conv2dGradFn.apply(x.contiguous(), relu, owner, 1, *([w] if layer.bias is None else [w, layer.bias]))
     return _Conv2dFn.apply(x.contiguous(), w, layer.bias, relu)

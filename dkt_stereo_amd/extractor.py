@@ -17,8 +17,8 @@ import torch.nn.functional as F
 from . import _ffi, norm_train, wcache
 import os
 
-from .conv import (conv2d, conv2d_fused, conv2d_fused_pair, conv2d_pair, conv2d_stats, fused_eligible,
-                   pair_eligible, stats_eligible)
+from .conv import (_autograd_eligible, conv2d, conv2d_autograd, conv2d_fused, conv2d_fused_pair, conv2d_pair, conv2d_stats,
+                   fused_eligible, pair_eligible, stats_eligible)
 
 #: DKT_FUSE_ENCODER=0: separate normalise / residual-join passes around the encoders' convolutions (A/B switch)
 FUSE_ENCODER = os.environ.get("DKT_FUSE_ENCODER", "1") != "0"
@@ -45,6 +45,14 @@ C8_ENCODER_CFG = 3
 #: tools/bench_encoder_train.py has shown arm b ahead of arm a by more than the a-to-a spread at both training shapes:
 #: not measured yet (DESIGN 3.15 holds the numbers that exist).
 TRAIN_NORM_NODES = False
+
+
+#: the encoders' convolutions under autograd (trainable weights or an input that requires grad) as conv.conv2d_autograd
+#: nodes -- forward on this library's kernels, backward on the pre-pass, dkt_conv2d_f16s_dscale / dkt_conv2d_wgrad and, for
+#: the down-sampling layers, dkt_conv2d_dgrad_s2 / dkt_conv2d_wgrad_s2 -- instead of nn.Conv2d (A/B handle).
+#: The rule of 3.15: on only once tools/bench_encoder_train.py has shown its arm ahead of arm a by more than the a-to-a
+#: spread at both training shapes.
+TRAIN_CONV_NODES = False
 
 
 def _hip_ok(x):
@@ -237,9 +245,13 @@ def add_relu(a, b):
 class _Conv2d(nn.Conv2d):
     """nn.Conv2d (same parameters, same state-dict keys) whose inference calls with stride 1 or 2
     go through dkt_stereo_amd.conv.conv2d (split-fp16 MFMA kernels; conv2d itself falls back to
-    the vendor convolution for shapes it does not cover); autograd and CPU are plain torch."""
+    the vendor convolution for shapes it does not cover); CPU is plain torch, and so is autograd unless TRAIN_CONV_NODES
+    is on: then an fp32 HIP call that autograd records is a conv.conv2d_autograd node."""
 
     def forward(self, x):
+        if (TRAIN_CONV_NODES and torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad)
+                and _hip_f32(x) and _autograd_eligible(x, self)):
+            return conv2d_autograd(x, self)
         if (x.is_cuda and x.dtype == torch.float32 and self.stride in ((1, 1), (2, 2)) and self.dilation == (1, 1)
                 and self.groups == 1 and not (torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad))):
             return conv2d(x, self)

@@ -967,8 +967,10 @@ class RAFTStereo(nn.Module):
         """raft_stereo.py:85-187 with test_mode=False: the up-sampled disparity of EVERY iteration (the sequence loss of
         tools/ft_dkt.py:223-242 weighs them), differentiable end to end.  The correlation block and the update operator run
         on this library's kernels as autograd nodes (corr._BuildFn / _LookupFn, conv.conv2d_autograd); the encoders'
-        convolutions fall back to torch wherever their weights need gradients (extractor._Conv2d), the feature encoder's
-        instance norms and residual joins around them are the nodes of norm_train.py when extractor.TRAIN_NORM_NODES is on."""
+        convolutions are conv.conv2d_autograd nodes too when extractor.TRAIN_CONV_NODES is on (stride 1 and the
+        down-sampling stride-2 layers alike; nn.Conv2d wherever their weights need gradients when it is off), the feature
+        encoder's instance norms and residual joins around them are the nodes of norm_train.py when
+        extractor.TRAIN_NORM_NODES is on; the context encoder's frozen batch norms stay torch."""
         args = self.args
         n = args.n_gru_layers
         image1 = (2 * (image1 / 255.0) - 1.0).contiguous()

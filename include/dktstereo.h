@@ -411,6 +411,38 @@ int dkt_conv2d_wgrad(const float *x, long x_bstride, const float *g, long g_bstr
                      float *gw /* (Cout,Cin,K,K) dense */, float *ws,
                      int B, int Cin, int Cout, int H, int W, int K, int device, void *stream);
 
+/* ---- backward of the encoders' stride-2 convolutions (training; core/extractor.py:6-60, :122-175 under training) ----
+ * torch autograd through conv2d(x, w, b, stride=2, padding=K/2), K in {1, 3}; x (B, Cin, H, W), g (B, Cout, Ho, Wo) the
+ * masked gradient g', Ho = (H-1)/2+1, Wo = (W-1)/2+1, any H, W >= 1.  fp32 NCHW, every batch element dense, batch strides
+ * in floats (views with a longer batch stride and pointers 4 bytes past a 16-byte boundary are fine).  scale is the device
+ * pair {s, 1/s} dkt_conv_grad_prepass leaves for g, read by the kernels, never by the host.
+ *
+ * dkt_conv2d_dgrad_s2: gx[b,ci,y,x] = sum g[b,co,oy,ox] * w[co,ci,ky,kx] over y = 2oy+ky-p, x = 2ox+kx-p.
+ *   w_hi/w_lo   dkt_conv2d_pack_weights of the input-gradient weight (w transposed over (Cout, Cin), rotated by 180
+ *               degrees: shape (Cin, Cout, K, K)) with src_channels = {Cout}, nsrc = 1; w_inv_scale = 1 / its scale.
+ *   Decomposed by output parity on the Ho x Wo grid (1 / 2 / 2 / 4 taps; nine products per pixel of g for K = 3): every
+ *   element of gx (B, Cin, H, W) is stored exactly once by the kernel, the zeros of a 1x1 layer's odd rows and columns
+ *   included -- no memset, no zero-inserted copy of g, no atomics; the same bits from run to run.  g * scale[0] and the
+ *   weight as fp16 hi + lo, three v_mfma_f32_32x32x16_f16 products, fp32 accumulation, un-scaled by scale[1] * w_inv_scale:
+ *   a power-of-two multiple of g gives that multiple of gx bit for bit.
+ *   Errors, before any device is touched: g, w_hi, w_lo, scale or gx null DKT_E_NULL; a size < 1, K not in {1, 3}, a batch
+ *   stride shorter than C*H*W of its tensor, or w_inv_scale not positive and finite DKT_E_SHAPE.
+ *
+ * dkt_conv2d_wgrad_s2: gw[co][ci][ky][kx] = sum_{b,oy,ox} g[b,co,oy,ox] * x[b,ci,2oy+ky-p,2ox+kx-p]; the contract of
+ *   dkt_conv2d_wgrad (operands split while staged, three products, split-K over (batch element, band of OUTPUT rows) into
+ *   ws, a finishing kernel that adds slices in ascending order and un-scales by scale[1] / x_scale; no float atomics, the
+ *   same bits for every grid size and for the 16-byte and the 4-byte load path; scale-equivariant bit for bit).  x is
+ *   de-interleaved into even and odd column planes while it is staged, so every LDS read stays aligned.
+ *   ws: dkt_conv2d_wgrad_s2_ws_floats(B, Cin, Cout, H, W, K) floats (H, W the INPUT size).  Errors as dkt_conv2d_wgrad. */
+int dkt_conv2d_dgrad_s2(const float *g, long g_bstride, const void *w_hi, const void *w_lo, float w_inv_scale,
+                        const float *scale /* device {s, 1/s} of g */, float *gx, long gx_bstride,
+                        int B, int Cin, int Cout, int H, int W, int K, int device, void *stream);
+long dkt_conv2d_wgrad_s2_ws_floats(int B, int Cin, int Cout, int H, int W, int K);
+int dkt_conv2d_wgrad_s2(const float *x, long x_bstride, const float *g, long g_bstride,
+                        const float *scale /* device {s, 1/s} of g */, float x_scale,
+                        float *gw /* (Cout,Cin,K,K) dense */, float *ws,
+                        int B, int Cin, int Cout, int H, int W, int K, int device, void *stream);
+
 /* dkt_conv2d_f16s (stride 1, no bias, no ReLU, no epilogue) with the activation scale in DEVICE memory: the input-gradient
  * convolution, whose operand range only the device knows.  scale = {s, 1/s} as dkt_conv_grad_prepass writes it:
  *   in_scale = scale[0],  out_scale = w_inv_scale * scale[1]   (w_inv_scale: 1 / the weight scale of the pack),
