@@ -747,15 +747,19 @@ def _batch_stride(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2] * t.shape[3]
 
 
+def _dense_per_batch(t):
+    """`t` itself when its batch elements are dense and do not overlap (a longer batch stride is fine), else a copy."""
+    B, C, H, W = t.shape
+    return t.contiguous() if not _dense(t) or (B > 1 and t.stride(0) < C * H * W) else t
+
+
 def conv_grad_prepass(gy, y=None, want_bias=True):
     """dkt_conv_grad_prepass on a dense-per-batch fp32 gradient: returns (g', gb, scale) -- g' = gy masked by y > 0 (gy
     itself without y), gb the per-channel sum of g' (None unless wanted), scale the device pair {2^e, 2^-e} of max|g'|."""
     _ffi.require_gpu(gy, *([] if y is None else [y]))
     B, C, H, W = gy.shape
-    if not _dense(gy) or (B > 1 and gy.stride(0) < C * H * W):
-        gy = gy.contiguous()
-    if y is not None and (not _dense(y) or (B > 1 and y.stride(0) < C * H * W)):
-        y = y.contiguous()
+    gy = _dense_per_batch(gy)
+    y = None if y is None else _dense_per_batch(y)
     L = _ffi.lib()
     gm = None if y is None else torch.empty((B, C, H, W), device=gy.device, dtype=torch.float32)
     gb = torch.empty(C, device=gy.device, dtype=torch.float32) if want_bias else None
@@ -790,30 +794,42 @@ GRAD_WEIGHT_HIP = True
 WGRAD_VENDOR_CLASSES = {(64, 64, 3): "73.8 vs 71.0 at 120x224, 55.0 vs 51.7 at 60x112, 49.4 vs 38.6 at 30x56"}
 
 
-def conv2d_wgrad(x, g, scale, k, x_scale=1.0):
-    """dkt_conv2d_wgrad: the (Cout, Cin, k, k) weight gradient of a stride-1 "same" k x k convolution (k in {1, 3}) from its
-    input `x` (B, Cin, H, W) and the masked gradient `g` (B, Cout, H, W), both fp32 with dense batch elements (`g` may be a
-    view with a longer batch stride); `scale` is the device pair {2^e, 2^-e} conv_grad_prepass left for `g`, `x_scale` the
-    host power of two of the layer's forward activations.  Nothing is read back on the host."""
+def _out_size_s2(H, W):
+    return (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+def conv2d_wgrad(x, g, scale, k, x_scale=1.0, stride=1):
+    """dkt_conv2d_wgrad / dkt_conv2d_wgrad_s2: the (Cout, Cin, k, k) weight gradient of a k x k convolution with padding k/2
+    (k in {1, 3}) and `stride` 1 or 2 from its input `x` (B, Cin, H, W) and the masked gradient `g` (B, Cout, H, W), at
+    stride 2 (B, Cout, Ho, Wo), both fp32 with dense batch elements (`g` may be a view with a longer batch stride); `scale`
+    is the device pair {2^e, 2^-e} conv_grad_prepass left for `g`, `x_scale` the host power of two of the layer's forward
+    activations.  Nothing is read back on the host."""
+    if stride not in (1, 2):
+        raise ValueError("conv2d_wgrad: stride %r is not 1 or 2" % (stride,))
+    name = "dkt_conv2d_wgrad" if stride == 1 else "dkt_conv2d_wgrad_s2"
     _ffi.require_gpu(x, g, scale)
     B, cin, H, W = x.shape
     cout = g.shape[1]
-    if tuple(g.shape) != (B, cout, H, W):
+    if stride == 1 and tuple(g.shape) != (B, cout, H, W):
         raise ValueError("conv2d_wgrad: g %s does not match x %s" % (tuple(g.shape), tuple(x.shape)))
-    if not _dense(x) or (B > 1 and x.stride(0) < cin * H * W):
-        x = x.contiguous()
-    if not _dense(g) or (B > 1 and g.stride(0) < cout * H * W):
-        g = g.contiguous()
+    if stride == 2 and tuple(g.shape) != (B, cout, *_out_size_s2(H, W)):
+        raise ValueError("conv2d_wgrad_s2: g %s is not the stride-2 gradient of x %s" % (tuple(g.shape), tuple(x.shape)))
+    x, g = _dense_per_batch(x), _dense_per_batch(g)
     L = _ffi.lib()
-    n = int(L.dkt_conv2d_wgrad_ws_floats(B, cin, cout, H, W, k))
+    n = int(getattr(L, name + "_ws_floats")(B, cin, cout, H, W, k))
     if n < 0:
-        _ffi.check(n, "dkt_conv2d_wgrad_ws_floats")
+        _ffi.check(n, name + "_ws_floats")
     gw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32)
     ws = torch.empty(n, device=x.device, dtype=torch.float32)
-    rc = L.dkt_conv2d_wgrad(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(), float(x_scale),
-                            gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, k, _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_wgrad")
+    rc = getattr(L, name)(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(), float(x_scale),
+                          gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, k, _ffi.device_of(x), _ffi.stream_of(x))
+    _ffi.check(rc, name)
     return gw
+
+
+def conv2d_wgrad_s2(x, g, scale, k, x_scale=1.0):
+    """conv2d_wgrad at stride 2."""
+    return conv2d_wgrad(x, g, scale, k, x_scale, stride=2)
 
 
 #: stride-2 (Cin, Cout, K) classes whose weight gradient stays on the vendor call with the handle on: rows of
@@ -821,10 +837,6 @@ def conv2d_wgrad(x, g, scale, k, x_scale=1.0):
 WGRAD_S2_VENDOR_CLASSES = {}
 #: ... and whose input gradient does (us of dkt_conv2d_dgrad_s2 vs us of torch.nn.grad.conv2d_input)
 DGRAD_S2_VENDOR_CLASSES = {}
-
-
-def _out_size_s2(H, W):
-    return (H - 1) // 2 + 1, (W - 1) // 2 + 1
 
 
 def conv2d_dgrad_s2(g, layer, scale, hw, pack_scale=None, out=None):
@@ -842,8 +854,7 @@ def conv2d_dgrad_s2(g, layer, scale, hw, pack_scale=None, out=None):
         raise ValueError("conv2d_dgrad_s2: g %s does not match the layer %s" % (tuple(g.shape), tuple(layer.weight.shape)))
     if (Ho, Wo) != _out_size_s2(H, W):
         raise ValueError("conv2d_dgrad_s2: g %s is not the stride-2 output of a %d x %d input" % (tuple(g.shape), H, W))
-    if not _dense(g) or (B > 1 and g.stride(0) < cout * Ho * Wo):
-        g = g.contiguous()
+    g = _dense_per_batch(g)
     pk = _packed_weights(layer, [cout], pack_scale)
     if out is None:
         gx = torch.empty((B, cin, H, W), device=g.device, dtype=torch.float32)
@@ -859,32 +870,6 @@ def conv2d_dgrad_s2(g, layer, scale, hw, pack_scale=None, out=None):
     return gx
 
 
-def conv2d_wgrad_s2(x, g, scale, k, x_scale=1.0):
-    """dkt_conv2d_wgrad_s2: the (Cout, Cin, k, k) weight gradient of a stride-2, padding k/2, k x k convolution (k in {1, 3})
-    from its input `x` (B, Cin, H, W) and the masked gradient `g` (B, Cout, Ho, Wo); arguments as conv2d_wgrad."""
-    _ffi.require_gpu(x, g, scale)
-    B, cin, H, W = x.shape
-    cout = g.shape[1]
-    Ho, Wo = _out_size_s2(H, W)
-    if tuple(g.shape) != (B, cout, Ho, Wo):
-        raise ValueError("conv2d_wgrad_s2: g %s is not the stride-2 gradient of x %s" % (tuple(g.shape), tuple(x.shape)))
-    if not _dense(x) or (B > 1 and x.stride(0) < cin * H * W):
-        x = x.contiguous()
-    if not _dense(g) or (B > 1 and g.stride(0) < cout * Ho * Wo):
-        g = g.contiguous()
-    L = _ffi.lib()
-    n = int(L.dkt_conv2d_wgrad_s2_ws_floats(B, cin, cout, H, W, k))
-    if n < 0:
-        _ffi.check(n, "dkt_conv2d_wgrad_s2_ws_floats")
-    gw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32)
-    ws = torch.empty(n, device=x.device, dtype=torch.float32)
-    rc = L.dkt_conv2d_wgrad_s2(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(),
-                               float(x_scale), gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, k, _ffi.device_of(x),
-                               _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_wgrad_s2")
-    return gw
-
-
 class _Conv2dGradFn(torch.autograd.Function):
     """conv2d_autograd with GRAD_PREPASS.  apply(x, relu, owner, nparts, *params): `owner` holds the (detached) weight and
     bias the kernels read and every packed image; `params` are the tensors autograd differentiates -- nparts weights, then
@@ -895,7 +880,7 @@ class _Conv2dGradFn(torch.autograd.Function):
         with torch.no_grad():
             y = conv2d(x.detach(), owner, relu=relu)
         ctx.owner, ctx.relu, ctx.nparts, ctx.has_bias = owner, bool(relu), nparts, len(params) > nparts
-        ctx.s2 = _stride_of(owner) == (2, 2)
+        ctx.stride = _stride_of(owner)[0]
         ctx.splits = [int(p.shape[0]) for p in params[:nparts]]
         ctx.save_for_backward(x, owner.weight, y if relu else None)
         return y
@@ -913,7 +898,7 @@ class _Conv2dGradFn(torch.autograd.Function):
             gy = gy if gy.dtype == torch.float32 else gy.float()
             shim = _grad_layer(ctx.owner) if need_x else None
             cls = (x.shape[1], w.shape[0], kh)
-            if ctx.s2:
+            if ctx.stride == 2:
                 # stride 2 (k in {1, 3}, _autograd_eligible): dkt_conv2d_dgrad_s2 / dkt_conv2d_wgrad_s2
                 dscale = need_x and get_backend() in _PASSES and cls not in DGRAD_S2_VENDOR_CLASSES
                 vendor_classes = WGRAD_S2_VENDOR_CLASSES
@@ -925,18 +910,15 @@ class _Conv2dGradFn(torch.autograd.Function):
             g, scale = gy, None
             if ctx.relu or need_b or dscale or wgrad:
                 g, gb, scale = conv_grad_prepass(gy, y if ctx.relu else None, want_bias=need_b)
-            if need_x and ctx.s2:
+            if need_x and ctx.stride == 2:
                 gx = (conv2d_dgrad_s2(g, shim, scale, x.shape[2:], shim.pack_scale) if dscale else
                       torch.nn.grad.conv2d_input(x.shape, w, g, stride=2, padding=(kh // 2, kw // 2)))
             elif need_x:
                 gx = conv2d_dscale(g, shim, scale, shim.pack_scale) if dscale else conv2d(g, shim)
-            if wgrad and ctx.s2:
-                gw = conv2d_wgrad_s2(x.detach(), g, scale, kh, 2.0 ** in_exp_of(ctx.owner))
-            elif wgrad:
-                gw = conv2d_wgrad(x.detach(), g, scale, kh, 2.0 ** in_exp_of(ctx.owner))
+            if wgrad:
+                gw = conv2d_wgrad(x.detach(), g, scale, kh, 2.0 ** in_exp_of(ctx.owner), ctx.stride)
             elif need_w:
-                gw = torch.nn.grad.conv2d_weight(x.detach(), w.shape, g, stride=2 if ctx.s2 else 1,
-                                                 padding=(kh // 2, kw // 2))
+                gw = torch.nn.grad.conv2d_weight(x.detach(), w.shape, g, stride=ctx.stride, padding=(kh // 2, kw // 2))
         gws = [None] * n if gw is None else list(gw.split(ctx.splits, 0)) if n > 1 else [gw]
         gbs = [None] * n if gb is None else list(gb.split(ctx.splits, 0)) if n > 1 else [gb]
         gws = [t if ctx.needs_input_grad[4 + i] else None for i, t in enumerate(gws)]

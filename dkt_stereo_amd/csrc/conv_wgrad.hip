@@ -1,23 +1,21 @@
 // conv_wgrad.hip -- the weight gradient of a stride-1 "same" convolution (dkt_stereo_amd/conv.py: _Conv2dGradFn.backward).
-// Reference: torch autograd through [relu](conv2d(x, w, b)) (core/update.py:9-10, 19-21, 72-76, 111-113 under training):
-//   gw[co][ci][ky][kx] = sum_{b,y,x} g'[b,co,y,x] * x[b,ci,y+ky-p,x+kx-p]          K in {1, 3}, p = K/2
+// Reference: torch autograd through [relu](conv2d(x, w, b)) (core/update.py:9-10, 19-21, 72-76, 111-113 under training).
+// The contract -- GEMM view, hi / lo split, slice plan, split-K workspace and its finishing kernel, which lives here for
+// both strides -- is in conv_wgrad_common.h; the reduction grid is H x W.  This file is the stride-1 staging scheme.
 //
-// GEMM view   D[co][(ci, tap)] = sum_{pixel} G[co][pixel] * X[ci][pixel + off(tap)]:  the reduction index is the pixel, the
-// contiguous axis of both operands in NCHW, so neither is transposed on the way into LDS.  Both are split into fp16 hi / lo
-// while they are staged (g' * scale[0] from the pre-pass, x * x_scale), the products are g_hi*x_hi + g_lo*x_hi + g_hi*x_lo on
-// v_mfma_f32_32x32x16_f16 with fp32 accumulation, as in conv2d.hip.
-//
-// Work item = (slice, 64 output channels, 64 input channels); block = 8 waves on one CU: waves 0..3 multiply -- each owns one
-// 32 x 32 fragment with all K*K taps in accumulators (144 registers for 3x3) -- and waves 4..7 stage, one of each kind per
-// SIMD.  A slice is (batch element, band of rows): the band height is a function of the shape alone (wgrad_plan).  The item
-// walks its band in pixel tiles of 2 rows x 32 columns through two LDS buffers (136 KiB):
+// Block = 8 waves on one CU: waves 0..3 multiply -- each owns one 32 x 32 fragment with all K*K taps in accumulators (144
+// registers for 3x3) -- and waves 4..7 stage, one of each kind per SIMD.  The item walks its band through two LDS buffers
+// (136 KiB):
 //   sg[buffer][hi|lo][co 64][2 x 32 pixels]                     pitch 144 B = 16 * 9
 //   sx[buffer][hi|lo][ci 64][2 + 2p rows][8 | 32 | 8 columns]   pitch 400 B = 16 * 25 (208 B = 16 * 13 for 1x1)
 // The staging waves hold two tiles in registers: the global loads of tile t + 1 are issued before tile t is split and
 // written, so their latency runs under that conversion and under the MFMAs of tile t - 1; one barrier per tile hands a
 // buffer over.  (The first form of this kernel staged and multiplied in the same four waves, two blocks per CU: its 144
 // accumulators left the staging addresses in scratch, every reload waited behind the tile's global loads, and the z|r layer
-// at 120 x 224 took 810 us against the 618 us of this form.)
+// at 120 x 224 took 810 us against the 618 us of this form.  This form is not free of scratch either: with 512 threads a
+// wave has 256 registers for both roles, and the 3x3 kernels compile to 256 VGPRs with 132 spilled, 532 B of scratch; the
+// 1x1 kernels to 130 / 132 VGPRs and none.  A compile-time fact -- what the spill costs on the device is not measured,
+// DESIGN 3.14.)
 // A k-step is 16 pixels of one row; lane l (channel l & 31, half h = l >> 5) reads the 8 pixels 8h.. of the step as ONE
 // aligned ds_read_b128: the 16 lanes the LDS serves together differ in the channel alone, and a channel pitch of 16 * odd
 // bytes spreads 16 channels over the 64 banks -- conflict-free.  The kx = +-1 taps are built in registers: the aligned block
@@ -25,46 +23,14 @@
 // dwords -- per k-step 2 + 18 reads for 27 MFMAs, under the 2-per-MFMA budget.  The column halo is one fp16 per row in the
 // last (first) slot of the left (right) 8-column pad; the rest of the pads is never used arithmetically.
 // Zero-fill: g' beyond W, beyond the band's last row and beyond Cout; x outside the image and beyond Cin.
-//
-// Split-K without float atomics: every item stores its partial tile to ws[slice][Cout][Cin][K][K]; the finishing kernel adds a
-// weight's slices in ascending order and un-scales by scale[1] / x_scale (powers of two).  Bit-identical from run to run,
-// for every grid size, and for the 16-byte and the 4-byte load path alike (they stage the same values).
-#include "dkt_common.h"
-#include <cmath>
+#include "conv_wgrad_common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#define WG_TH 2               // rows of a pixel tile
-#define WG_TW 32              // columns of a pixel tile
-#define WG_CB 64              // channels of a block tile, on both sides
 #define WG_XROW 48            // fp16 per staged x row: 8 pad | 32 | 8 pad
-#define WG_GP 72              // fp16 per staged g' channel: 64 + 8 pad
-#define WG_T0 2048            // pixels per slice the plan starts from ...
-#define WG_TMIN 512           // ... and does not go below
-#define WG_ITEMS 256          // work items the plan asks for before it stops halving
 
 struct WgradArgs {
-    const float *x, *g, *scale;
-    float x_scale;
-    float *ws;
-    long x_bs, g_bs;
-    int B, Cin, Cout, H, W;
-    int rows_band, bands;     // slice = b * bands + band
-    int n_co, n_ci, tiles_w;
-    long items;               // item = (slice * n_co + co block) * n_ci + ci block
+    WGRAD_ARGS_OPERANDS
+    WGRAD_ARGS_SLICES
 };
-
-__device__ __forceinline__ void wgrad_split8(const float (&v)[8], float s, f16x8 &hi, f16x8 &lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float t = __fmul_rn(v[j], s);
-        const _Float16 h = (_Float16)t;
-        hi[j] = h;
-        lo[j] = (_Float16)__fsub_rn(t, (float)h);
-    }
-}
 
 // 8 consecutive floats of a row from column iw on; zero from column W on (V = 4: W % 4 == 0, a float4 is inside or outside)
 template <int V>
@@ -296,33 +262,19 @@ __global__ __launch_bounds__(256) void conv_wgrad_finish_kernel(WgradFinishArgs 
     }
 }
 
-struct WgradPlan {
-    int rows_band, bands, n_co, n_ci;
-};
-
-// The slice rule: bands of (T / W rounded down to whole pixel tiles, at least one) rows, T = 2048 pixels halved down to 512
-// while the problem has fewer than 256 work items.  A function of the shape alone.
-static WgradPlan wgrad_plan(int B, int Cin, int Cout, int H, int W) {
-    WgradPlan p;
-    p.n_co = (Cout + WG_CB - 1) / WG_CB;
-    p.n_ci = (Cin + WG_CB - 1) / WG_CB;
-    for (long T = WG_T0;; T >>= 1) {
-        const long rows = (T / W) & ~(long)(WG_TH - 1);
-        p.rows_band = (int)(rows < WG_TH ? WG_TH : rows);
-        p.bands = (H + p.rows_band - 1) / p.rows_band;
-        if ((long)p.n_co * p.n_ci * B * p.bands >= WG_ITEMS || T <= WG_TMIN) break;
-    }
-    return p;
-}
-
-static bool wgrad_shape_ok(int B, int Cin, int Cout, int H, int W, int K) {
-    return B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && (K == 1 || K == 3);
+int wgrad_finish(const float *ws, const float *scale, float x_scale, float *gw, long E, int nslices, hipStream_t st) {
+    WgradFinishArgs f;
+    f.ws = ws; f.scale = scale; f.inv_x_scale = 1.0f / x_scale; f.gw = gw;
+    f.E = E;
+    f.nslices = nslices;
+    const long fb = (E + 255) / 256;
+    hipLaunchKernelGGL(conv_wgrad_finish_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, f);
+    return dkt_launch_status();
 }
 
 extern "C" long dkt_conv2d_wgrad_ws_floats(int B, int Cin, int Cout, int H, int W, int K) {
     if (!wgrad_shape_ok(B, Cin, Cout, H, W, K)) return DKT_E_SHAPE;
-    const WgradPlan p = wgrad_plan(B, Cin, Cout, H, W);
-    return (long)B * p.bands * Cout * Cin * K * K;
+    return wgrad_ws_floats(B, Cin, Cout, H, W, K);
 }
 
 extern "C" int dkt_conv2d_wgrad(const float *x, long x_bstride, const float *g, long g_bstride, const float *scale,
@@ -332,25 +284,14 @@ extern "C" int dkt_conv2d_wgrad(const float *x, long x_bstride, const float *g, 
     if (!wgrad_shape_ok(B, Cin, Cout, H, W, K)) return DKT_E_SHAPE;
     const long HW = (long)H * W;
     if (x_bstride < (long)Cin * HW || g_bstride < (long)Cout * HW) return DKT_E_SHAPE;
-    int xe = 0;
-    if (!(x_scale > 0.0f) || !std::isfinite(x_scale) || std::frexp(x_scale, &xe) != 0.5f || !std::isfinite(1.0f / x_scale))
-        return DKT_E_SHAPE;
+    if (!wgrad_x_scale_ok(x_scale)) return DKT_E_SHAPE;
     DKT_ENTER(device);
-    int dev = device, cus = 0;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
     const WgradPlan p = wgrad_plan(B, Cin, Cout, H, W);
     WgradArgs a;
-    a.x = x; a.g = g; a.scale = scale; a.x_scale = x_scale; a.ws = ws;
-    a.x_bs = x_bstride; a.g_bs = g_bstride;
-    a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-    a.rows_band = p.rows_band; a.bands = p.bands; a.n_co = p.n_co; a.n_ci = p.n_ci;
-    a.tiles_w = (W + WG_TW - 1) / WG_TW;
-    a.items = (long)B * p.bands * p.n_co * p.n_ci;
+    wgrad_fill_args(a, x, x_bstride, g, g_bstride, scale, x_scale, ws, B, Cin, Cout, H, W, p, W);
     const bool vec = (W % 4 == 0) && (x_bstride % 4 == 0) && (g_bstride % 4 == 0) &&
                      ((uintptr_t)x % 16 == 0) && ((uintptr_t)g % 16 == 0);
-    const long slots = cus;                                    // one block of 8 waves per CU (136 KiB of LDS)
-    const unsigned blocks = (unsigned)(a.items < slots ? a.items : slots);
+    const unsigned blocks = wgrad_blocks(a.items, device);     // one block of 8 waves per CU (136 KiB of LDS)
     hipStream_t st = (hipStream_t)stream;
     if (K == 3) {
         if (vec) hipLaunchKernelGGL((conv_wgrad_kernel<3, 4>), dim3(blocks), dim3(512), 0, st, a);
@@ -359,13 +300,7 @@ extern "C" int dkt_conv2d_wgrad(const float *x, long x_bstride, const float *g, 
         if (vec) hipLaunchKernelGGL((conv_wgrad_kernel<1, 4>), dim3(blocks), dim3(512), 0, st, a);
         else hipLaunchKernelGGL((conv_wgrad_kernel<1, 1>), dim3(blocks), dim3(512), 0, st, a);
     }
-    int rc = dkt_launch_status();
+    const int rc = dkt_launch_status();
     if (rc != DKT_OK) return rc;
-    WgradFinishArgs f;
-    f.ws = ws; f.scale = scale; f.inv_x_scale = 1.0f / x_scale; f.gw = gw;
-    f.E = (long)Cout * Cin * K * K;
-    f.nslices = B * p.bands;
-    const long fb = (f.E + 255) / 256;
-    hipLaunchKernelGGL(conv_wgrad_finish_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, f);
-    return dkt_launch_status();
+    return wgrad_finish(ws, scale, x_scale, gw, (long)Cout * Cin * K * K, B * p.bands, st);
 }

@@ -1,13 +1,8 @@
 // conv_wgrad_s2.hip -- the weight gradient of a stride-2, padding K/2 convolution, K in {1, 3} (dkt_stereo_amd/conv.py:
 // _Conv2dGradFn.backward for the encoders' down-sampling layers).
-// Reference: torch autograd through conv2d(x, w, b, stride=2) (core/extractor.py:6-60, :122-175 under training):
-//   gw[co][ci][ky][kx] = sum_{b,oy,ox} g'[b,co,oy,ox] * x[b,ci,2oy+ky-p,2ox+kx-p]          p = K/2
-//
-// The contract of conv_wgrad.hip: D[co][(ci, tap)] = sum_{pixel} G[co][pixel] * X[ci][pixel'], the reduction index is the
-// pixel of g' (Ho x Wo); both operands are split into fp16 hi / lo while they are staged (g' * scale[0] from the pre-pass,
-// x * x_scale), g_hi*x_hi + g_lo*x_hi + g_hi*x_lo on v_mfma_f32_32x32x16_f16 with fp32 accumulation; split-K over (batch
-// element, band of output rows) into a workspace, a finishing kernel adds a weight's slices in ascending order and un-scales:
-// no float atomics, the same bits for every grid size and for the 16-byte and the 4-byte load path.
+// Reference: torch autograd through conv2d(x, w, b, stride=2) (core/extractor.py:6-60, :122-175 under training).
+// The contract -- GEMM view, hi / lo split, slice plan, split-K workspace and its finishing kernel -- is in
+// conv_wgrad_common.h; the reduction grid is the Ho x Wo of g'.  This file is the stride-2 staging scheme.
 //
 // Stride 2 breaks the unit pixel stride the stride-1 kernel's aligned reads rest on, so x is DE-INTERLEAVED while it is
 // staged: a row of x becomes an even plane E[c] = x[2c] and an odd plane O[c] = x[2c + 1], and for 8 consecutive ox
@@ -21,43 +16,17 @@
 // block has the CU's registers to itself, so nothing spills).  Every wave stages and multiplies: the global loads of tile
 // t + 1 are issued before the MFMAs of tile t and consumed after them.
 // Zero-fill: g' beyond Wo, beyond the band's last row and beyond Cout; x outside the image and beyond Cin.
-#include "dkt_common.h"
-#include <cmath>
+#include "conv_wgrad_common.h"
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-#define W2_TH 2               // output rows of a pixel tile
-#define W2_TW 32              // output columns of a pixel tile
-#define W2_CB 64              // channels of a block tile, on both sides
 #define W2_XROW 72            // fp16 per staged x row: E 32 | 8 pad | O 32
-#define W2_GP 72              // fp16 per staged g' channel: 64 + 8 pad
-#define W2_T0 2048            // output pixels per slice the plan starts from ...
-#define W2_TMIN 512           // ... and does not go below
-#define W2_ITEMS 256          // work items the plan asks for before it stops halving
 
 struct WgradS2Args {
-    const float *x, *g, *scale;
-    float x_scale;
-    float *ws;
-    long x_bs, g_bs;
-    int B, Cin, Cout, H, W, Ho, Wo;
-    int rows_band, bands;     // slice = b * bands + band; bands of OUTPUT rows
-    int n_co, n_ci, tiles_w;
-    long items;               // item = (slice * n_co + co block) * n_ci + ci block
+    WGRAD_ARGS_OPERANDS
+    int Ho, Wo;
+    WGRAD_ARGS_SLICES
 };
 
-__device__ __forceinline__ void w2_split8(const float (&v)[8], float s, f16x8 &hi, f16x8 &lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float t = __fmul_rn(v[j], s);
-        const _Float16 h = (_Float16)t;
-        hi[j] = h;
-        lo[j] = (_Float16)__fsub_rn(t, (float)h);
-    }
-}
-
+// (conv_wgrad.hip keeps a load of its own: with this template its instruction stream changes)
 // N consecutive floats of a row from column iw on; zero from column W on (V = 4: W % 4 == 0, a float4 is inside or outside)
 template <int V, int N>
 __device__ __forceinline__ void w2_load(const float *row, int iw, int W, bool ok, float (&v)[N]) {
@@ -76,13 +45,13 @@ __device__ __forceinline__ void w2_load(const float *row, int iw, int W, bool ok
 template <int KS, int V>
 __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
     constexpr int TAPS = KS * KS;
-    constexpr int XR = KS == 3 ? 2 * W2_TH + 1 : W2_TH;         // staged x rows
+    constexpr int XR = KS == 3 ? 2 * WG_TH + 1 : WG_TH;         // staged x rows
     constexpr int XP = XR * W2_XROW + (KS == 3 ? 0 : 8);        // fp16 per staged x channel: 16 * odd bytes
-    constexpr int GU = W2_CB * W2_TH * 4 / 256;                 // 8-pixel units of g' per thread
-    constexpr int XU = W2_CB * XR * 4 / 256;                    // 16-column units of x per thread
-    constexpr int HN = W2_CB * XR;                              // halo elements (K = 3)
+    constexpr int GU = WG_CB * WG_TH * 4 / 256;                 // 8-pixel units of g' per thread
+    constexpr int XU = WG_CB * XR * 4 / 256;                    // 16-column units of x per thread
+    constexpr int HN = WG_CB * XR;                              // halo elements (K = 3)
     constexpr int HU = (HN + 255) / 256;
-    constexpr int SGN = W2_CB * W2_GP, SXN = W2_CB * XP;        // fp16 per plane
+    constexpr int SGN = WG_CB * WG_GP, SXN = WG_CB * XP;        // fp16 per plane
     __shared__ __attribute__((aligned(16))) _Float16 sg[2][SGN];           // [hi | lo]
     __shared__ __attribute__((aligned(16))) _Float16 sx[2][SXN];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -102,19 +71,19 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
         const int band = slice % a.bands, b = slice / a.bands;
         const int r0 = band * a.rows_band;
         const int r1 = min(a.Ho, r0 + a.rows_band);
-        const int ntiles = ((r1 - r0 + W2_TH - 1) / W2_TH) * a.tiles_w;
+        const int ntiles = ((r1 - r0 + WG_TH - 1) / WG_TH) * a.tiles_w;
         const float *gb = a.g + (long)b * a.g_bs;
         const float *xb = a.x + (long)b * a.x_bs;
         float gv[GU][8], xv[XU][16], hv[HU];
 
         auto load = [&](int tile) {
-            const int th0 = r0 + (tile / a.tiles_w) * W2_TH;
-            const int tw0 = (tile % a.tiles_w) * W2_TW;
+            const int th0 = r0 + (tile / a.tiles_w) * WG_TH;
+            const int tw0 = (tile % a.tiles_w) * WG_TW;
 #pragma unroll
             for (int i = 0; i < GU; ++i) {
                 const int u = tid + 256 * i;
-                const int grp = u & 3, row = (u >> 2) & (W2_TH - 1), ch = u >> 3;
-                const int co = cob * W2_CB + ch, oy = th0 + row;
+                const int grp = u & 3, row = (u >> 2) & (WG_TH - 1), ch = u >> 3;
+                const int co = cob * WG_CB + ch, oy = th0 + row;
                 const bool ok = co < a.Cout && oy < r1;
                 w2_load<V, 8>(gb + (ok ? (long)co * HoWo + (long)oy * a.Wo : 0L), tw0 + grp * 8, a.Wo, ok, gv[i]);
             }
@@ -122,7 +91,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
             for (int i = 0; i < XU; ++i) {
                 const int u = tid + 256 * i;
                 const int grp = u & 3, xr = (u >> 2) % XR, ch = (u >> 2) / XR;
-                const int ci = cib * W2_CB + ch, ih = KS == 3 ? 2 * th0 - 1 + xr : 2 * (th0 + xr);
+                const int ci = cib * WG_CB + ch, ih = KS == 3 ? 2 * th0 - 1 + xr : 2 * (th0 + xr);
                 const bool ok = ci < a.Cin && ih >= 0 && ih < a.H;
                 w2_load<V, 16>(xb + (ok ? (long)ci * HW + (long)ih * a.W : 0L), 2 * tw0 + grp * 16, a.W, ok, xv[i]);
             }
@@ -131,7 +100,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
                 for (int i = 0; i < HU; ++i) {
                     const int u = tid + 256 * i;
                     const int xr = u % XR, ch = u / XR;
-                    const int ci = cib * W2_CB + ch, ih = 2 * th0 - 1 + xr, iw = 2 * tw0 - 1;
+                    const int ci = cib * WG_CB + ch, ih = 2 * th0 - 1 + xr, iw = 2 * tw0 - 1;
                     const bool ok = u < HN && ci < a.Cin && ih >= 0 && ih < a.H && iw >= 0 && iw < a.W;
                     hv[i] = ok ? xb[(long)ci * HW + (long)ih * a.W + iw] : 0.0f;
                 }
@@ -141,10 +110,10 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
 #pragma unroll
             for (int i = 0; i < GU; ++i) {
                 const int u = tid + 256 * i;
-                const int grp = u & 3, row = (u >> 2) & (W2_TH - 1), ch = u >> 3;
+                const int grp = u & 3, row = (u >> 2) & (WG_TH - 1), ch = u >> 3;
                 f16x8 hi, lo;
-                w2_split8(gv[i], gs, hi, lo);
-                const int o = ch * W2_GP + row * W2_TW + grp * 8;
+                wgrad_split8(gv[i], gs, hi, lo);
+                const int o = ch * WG_GP + row * WG_TW + grp * 8;
                 *(f16x8 *)&sg[0][o] = hi;
                 *(f16x8 *)&sg[1][o] = lo;
             }
@@ -160,11 +129,11 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
                 }
                 f16x8 hi, lo;
                 const int o = ch * XP + xr * W2_XROW + grp * 8;
-                w2_split8(ev, xs, hi, lo);
+                wgrad_split8(ev, xs, hi, lo);
                 *(f16x8 *)&sx[0][o] = hi;
                 *(f16x8 *)&sx[1][o] = lo;
                 if constexpr (KS == 3) {
-                    w2_split8(ov, xs, hi, lo);
+                    wgrad_split8(ov, xs, hi, lo);
                     *(f16x8 *)&sx[0][o + 40] = hi;
                     *(f16x8 *)&sx[1][o + 40] = lo;
                 }
@@ -196,14 +165,14 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
             store();
             __syncthreads();                                   // tile `tile` is staged
             if (tile + 1 < ntiles) load(tile + 1);             // in flight under the MFMAs below
-            const _Float16 *pg = &sg[0][(wco * 32 + r) * W2_GP + 8 * h];
+            const _Float16 *pg = &sg[0][(wco * 32 + r) * WG_GP + 8 * h];
             const _Float16 *px = &sx[0][(wci * 32 + r) * XP + 8 * h];
             // ---- 4 k-steps of 16 output pixels: (row, 16-column half)
 #pragma unroll
-            for (int st = 0; st < W2_TH * 2; ++st) {
+            for (int st = 0; st < WG_TH * 2; ++st) {
                 const int row = st >> 1, cb = (st & 1) * 16;
-                const f16x8 ahi = *(const f16x8 *)(pg + row * W2_TW + cb);
-                const f16x8 alo = *(const f16x8 *)(pg + SGN + row * W2_TW + cb);
+                const f16x8 ahi = *(const f16x8 *)(pg + row * WG_TW + cb);
+                const f16x8 alo = *(const f16x8 *)(pg + SGN + row * WG_TW + cb);
 #pragma unroll
                 for (int ky = 0; ky < KS; ++ky) {
                     const _Float16 *q = px + (KS == 3 ? 2 * row + ky : row) * W2_XROW + cb;
@@ -240,12 +209,12 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
             __syncthreads();                                   // the tile has been read
         }
         // ---- the partial tile: D[row = co][col = ci], col = lane & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5)
-        const int ci = cib * W2_CB + wci * 32 + r;
+        const int ci = cib * WG_CB + wci * 32 + r;
         float *wp = a.ws + (long)slice * E;
         if (ci < a.Cin) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int co = cob * W2_CB + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                const int co = cob * WG_CB + wco * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
                 if (co < a.Cout) {
                     float *p = wp + ((long)co * a.Cin + ci) * TAPS;
 #pragma unroll
@@ -256,80 +225,27 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_s2_kernel(WgradS2Args a) {
     }
 }
 
-struct WgradS2FinishArgs {
-    const float *ws, *scale;
-    float inv_x_scale;
-    float *gw;
-    long E;
-    int nslices;
-};
-
-// One thread per weight: its slices in ascending order, then the un-scaling (a power of two).
-__global__ __launch_bounds__(256) void conv_wgrad_s2_finish_kernel(WgradS2FinishArgs a) {
-    const float un = __fmul_rn(a.scale[1], a.inv_x_scale);
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < a.E; e += (long)gridDim.x * 256) {
-        float s = 0.0f;
-#pragma unroll 4
-        for (int k = 0; k < a.nslices; ++k) s = __fadd_rn(s, a.ws[(long)k * a.E + e]);
-        a.gw[e] = __fmul_rn(s, un);
-    }
-}
-
-struct WgradS2Plan {
-    int rows_band, bands, n_co, n_ci;
-};
-
-// The slice rule of conv_wgrad.hip on the OUTPUT grid: bands of (T / Wo rounded down to whole pixel tiles, at least one)
-// output rows, T = 2048 output pixels halved down to 512 while the problem has fewer than 256 work items.
-static WgradS2Plan wgrad_s2_plan(int B, int Cin, int Cout, int Ho, int Wo) {
-    WgradS2Plan p;
-    p.n_co = (Cout + W2_CB - 1) / W2_CB;
-    p.n_ci = (Cin + W2_CB - 1) / W2_CB;
-    for (long T = W2_T0;; T >>= 1) {
-        const long rows = (T / Wo) & ~(long)(W2_TH - 1);
-        p.rows_band = (int)(rows < W2_TH ? W2_TH : rows);
-        p.bands = (Ho + p.rows_band - 1) / p.rows_band;
-        if ((long)p.n_co * p.n_ci * B * p.bands >= W2_ITEMS || T <= W2_TMIN) break;
-    }
-    return p;
-}
-
-static bool wgrad_s2_shape_ok(int B, int Cin, int Cout, int H, int W, int K) {
-    return B > 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0 && (K == 1 || K == 3);
-}
-
 extern "C" long dkt_conv2d_wgrad_s2_ws_floats(int B, int Cin, int Cout, int H, int W, int K) {
-    if (!wgrad_s2_shape_ok(B, Cin, Cout, H, W, K)) return DKT_E_SHAPE;
-    const WgradS2Plan p = wgrad_s2_plan(B, Cin, Cout, (H - 1) / 2 + 1, (W - 1) / 2 + 1);
-    return (long)B * p.bands * Cout * Cin * K * K;
+    if (!wgrad_shape_ok(B, Cin, Cout, H, W, K)) return DKT_E_SHAPE;
+    return wgrad_ws_floats(B, Cin, Cout, (H - 1) / 2 + 1, (W - 1) / 2 + 1, K);
 }
 
 extern "C" int dkt_conv2d_wgrad_s2(const float *x, long x_bstride, const float *g, long g_bstride, const float *scale,
                                    float x_scale, float *gw, float *ws, int B, int Cin, int Cout, int H, int W, int K,
                                    int device, void *stream) {
     if (!x || !g || !scale || !gw || !ws) return DKT_E_NULL;
-    if (!wgrad_s2_shape_ok(B, Cin, Cout, H, W, K)) return DKT_E_SHAPE;
+    if (!wgrad_shape_ok(B, Cin, Cout, H, W, K)) return DKT_E_SHAPE;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     if (x_bstride < (long)Cin * H * W || g_bstride < (long)Cout * Ho * Wo) return DKT_E_SHAPE;
-    int xe = 0;
-    if (!(x_scale > 0.0f) || !std::isfinite(x_scale) || std::frexp(x_scale, &xe) != 0.5f || !std::isfinite(1.0f / x_scale))
-        return DKT_E_SHAPE;
+    if (!wgrad_x_scale_ok(x_scale)) return DKT_E_SHAPE;
     DKT_ENTER(device);
-    int dev = device, cus = 0;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    const WgradS2Plan p = wgrad_s2_plan(B, Cin, Cout, Ho, Wo);
+    const WgradPlan p = wgrad_plan(B, Cin, Cout, Ho, Wo);
     WgradS2Args a;
-    a.x = x; a.g = g; a.scale = scale; a.x_scale = x_scale; a.ws = ws;
-    a.x_bs = x_bstride; a.g_bs = g_bstride;
-    a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-    a.rows_band = p.rows_band; a.bands = p.bands; a.n_co = p.n_co; a.n_ci = p.n_ci;
-    a.tiles_w = (Wo + W2_TW - 1) / W2_TW;
-    a.items = (long)B * p.bands * p.n_co * p.n_ci;
+    wgrad_fill_args(a, x, x_bstride, g, g_bstride, scale, x_scale, ws, B, Cin, Cout, H, W, p, Wo);
+    a.Ho = Ho; a.Wo = Wo;
     const bool vec = (W % 4 == 0) && (Wo % 4 == 0) && (x_bstride % 4 == 0) && (g_bstride % 4 == 0) &&
                      ((uintptr_t)x % 16 == 0) && ((uintptr_t)g % 16 == 0);
-    const long slots = cus;                                    // one block per CU (108 KiB of LDS)
-    const unsigned blocks = (unsigned)(a.items < slots ? a.items : slots);
+    const unsigned blocks = wgrad_blocks(a.items, device);     // one block per CU (108 KiB of LDS)
     hipStream_t st = (hipStream_t)stream;
     if (K == 3) {
         if (vec) hipLaunchKernelGGL((conv_wgrad_s2_kernel<3, 4>), dim3(blocks), dim3(256), 0, st, a);
@@ -338,13 +254,7 @@ extern "C" int dkt_conv2d_wgrad_s2(const float *x, long x_bstride, const float *
         if (vec) hipLaunchKernelGGL((conv_wgrad_s2_kernel<1, 4>), dim3(blocks), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((conv_wgrad_s2_kernel<1, 1>), dim3(blocks), dim3(256), 0, st, a);
     }
-    int rc = dkt_launch_status();
+    const int rc = dkt_launch_status();
     if (rc != DKT_OK) return rc;
-    WgradS2FinishArgs f;
-    f.ws = ws; f.scale = scale; f.inv_x_scale = 1.0f / x_scale; f.gw = gw;
-    f.E = (long)Cout * Cin * K * K;
-    f.nslices = B * p.bands;
-    const long fb = (f.E + 255) / 256;
-    hipLaunchKernelGGL(conv_wgrad_s2_finish_kernel, dim3((unsigned)(fb < 4096 ? fb : 4096)), dim3(256), 0, st, f);
-    return dkt_launch_status();
+    return wgrad_finish(ws, scale, x_scale, gw, (long)Cout * Cin * K * K, B * p.bands, st);
 }

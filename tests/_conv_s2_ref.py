@@ -41,8 +41,8 @@ LAYOUTS = R.LAYOUTS
 GX_BOUND = R.GX_BOUND
 A_BOUND = WR.A_BOUND
 U = R.U
-#: the weight-gradient kernel's tiling (csrc/conv_wgrad_s2.hip): channels per block, output rows of a pixel tile, the plan
-BLOCK, TILE_ROWS, T0, TMIN, ITEMS = 64, 2, 2048, 512, 256
+#: the weight-gradient kernels' tiling (csrc/conv_wgrad_common.h): channels per block, output rows of a pixel tile
+BLOCK, TILE_ROWS = WR.BLOCK, WR.TILE_ROWS
 
 
 def out_size(H, W):
@@ -70,18 +70,10 @@ def masked(case, m=0):
 
 
 def plan(case):
-    """(output rows per band, bands, output-channel blocks, input-channel blocks) of dkt_conv2d_wgrad_s2: wgrad_s2_plan
-    restated -- the rule of dkt_conv2d_wgrad on the Ho x Wo grid.  Slices of one weight: B * bands."""
+    """(output rows per band, bands, output-channel blocks, input-channel blocks) of dkt_conv2d_wgrad_s2: the rule of
+    dkt_conv2d_wgrad (_conv_wgrad_ref.grid_plan) on the Ho x Wo grid.  Slices of one weight: B * bands."""
     B, H, W, k, cin, cout = case
-    Ho, Wo = out_size(H, W)
-    n_co, n_ci = -(-cout // BLOCK), -(-cin // BLOCK)
-    T = T0
-    while True:
-        rows = max(TILE_ROWS, (T // Wo) // TILE_ROWS * TILE_ROWS)
-        bands = -(-Ho // rows)
-        if n_co * n_ci * B * bands >= ITEMS or T <= TMIN:
-            return rows, bands, n_co, n_ci
-        T //= 2
+    return WR.grid_plan(B, *out_size(H, W), cin, cout)
 
 
 def bands_of(case):
@@ -120,16 +112,11 @@ b_ratio = WR.b_ratio
 
 
 def b_bound(x, gp, k):
-    n = gp.shape[0] * gp.shape[2] * gp.shape[3]
-    return (3.0 * 2.0 ** -22 + n * U / (1.0 - n * U)) * _cw(x.double().abs(), gp.double().abs(), k)
+    return WR.b_factor(gp.shape[0] * gp.shape[2] * gp.shape[3]) * _cw(x.double().abs(), gp.double().abs(), k)
 
 
 # ------------------------------------------------------------------------------------------------------------ emulation
-def _split32(t, scale):
-    s = t * scale                                   # fp32, a power of two: exact
-    hi = s.half()
-    lo = (s - hi.float()).half()
-    return hi.float(), lo.float()
+_split32 = WR._split32
 
 
 def _taps(k, parity):

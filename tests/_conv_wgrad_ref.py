@@ -27,7 +27,7 @@ KS = R.KS
 LAYOUTS = R.LAYOUTS
 A_BOUND = R.GX_BOUND
 U = R.U
-#: the kernel's tiling (csrc/conv_wgrad.hip): channels per block on both sides, rows of a pixel tile, the plan's constants
+#: the kernels' tiling (csrc/conv_wgrad_common.h): channels per block on both sides, rows of a pixel tile, the plan's constants
 BLOCK, TILE_ROWS, T0, TMIN, ITEMS = 64, 2, 2048, 512, 256
 
 
@@ -45,18 +45,23 @@ def inputs(case):
     return x, w, b, gy
 
 
-def plan(case):
-    """(rows per band, bands, output-channel blocks, input-channel blocks) of dkt_conv2d_wgrad for the case: the slice rule
+def grid_plan(B, rows, cols, cin, cout):
+    """(rows per band, bands, output-channel blocks, input-channel blocks) on a rows x cols reduction grid: the slice rule
     of wgrad_plan restated.  Slices of one weight: B * bands."""
-    B, H, W, k, cin, cout = case
     n_co, n_ci = -(-cout // BLOCK), -(-cin // BLOCK)
     T = T0
     while True:
-        rows = max(TILE_ROWS, (T // W) // TILE_ROWS * TILE_ROWS)
-        bands = -(-H // rows)
+        band = max(TILE_ROWS, (T // cols) // TILE_ROWS * TILE_ROWS)
+        bands = -(-rows // band)
         if n_co * n_ci * B * bands >= ITEMS or T <= TMIN:
-            return rows, bands, n_co, n_ci
+            return band, bands, n_co, n_ci
         T //= 2
+
+
+def plan(case):
+    """grid_plan of dkt_conv2d_wgrad for the case: the grid is H x W."""
+    B, H, W, k, cin, cout = case
+    return grid_plan(B, H, W, cin, cout)
 
 
 def _cw(x, gp, k):
@@ -77,9 +82,13 @@ def a_error(got, exact):
     return R.gx_error(got, exact)
 
 
+def b_factor(n):
+    """3 * 2^-22 + gamma_n of bound (b)."""
+    return 3.0 * 2.0 ** -22 + n * U / (1.0 - n * U)
+
+
 def b_bound(x, gp, k):
-    n = x.shape[0] * x.shape[2] * x.shape[3]
-    return (3.0 * 2.0 ** -22 + n * U / (1.0 - n * U)) * abs_sum(x, gp, k)
+    return b_factor(x.shape[0] * x.shape[2] * x.shape[3]) * abs_sum(x, gp, k)
 
 
 def b_ratio(got, exact, bound):
