@@ -129,3 +129,65 @@ def split_conv(g, w, in_scale):
     pad = w.shape[2] // 2
     acc = F.conv2d(ghi, whi, padding=pad) + F.conv2d(ghi, wlo, padding=pad) + F.conv2d(glo, whi, padding=pad)
     return acc / (in_scale * ws)
+
+
+# ------------------------------------------------------------------------------------ the pre-pass beyond one segment
+#: csrc/conv_grad.hip: elements per work item, the widest launch, threads of the finish
+PRE_SEG, PRE_BLOCKS, PRE_THREADS = 4096, 2048, 256
+#: (B, C, H, W) that take dkt_conv_grad_prepass out of "one segment per plane, one item per block, one channel per thread"
+PREPASS_PLAN_CASES = [
+    (2, 520, 41, 100),           # HW = 4100: two segments, the last 4 elements long; 2080 items; a finish thread owns 3 channels
+    (3, 300, 67, 123),           # HW = 8241 = 2 * 4096 + 49, not a multiple of 4: the 4-byte path only; 2700 items with C < 512
+    (3, 2, 128, 96),             # HW = 12288: three whole segments
+]
+PREPASS_PLAN_IDS = ["x".join(str(v) for v in c) for c in PREPASS_PLAN_CASES]
+
+
+def prepass_regime(case):
+    """dict of nseg (segments per plane), last (elements of the last segment), items, per_thread (channels the busiest
+    finish thread owns), vec (HW % 4 == 0: the 16-byte path can run)."""
+    B, C, H, W = case
+    HW = H * W
+    nseg = -(-HW // PRE_SEG)
+    return dict(nseg=nseg, last=HW - (nseg - 1) * PRE_SEG, items=B * C * nseg, per_thread=-(-C // PRE_THREADS),
+                vec=HW % 4 == 0)
+
+
+@functools.lru_cache(maxsize=None)
+def prepass_inputs(case):
+    """(gy, y) of a pre-pass case: fp32, CPU, seeded by the case."""
+    B, C, H, W = case
+    g = torch.Generator().manual_seed(3000 + PREPASS_PLAN_CASES.index(case))
+    return torch.randn(B, C, H, W, generator=g), torch.randn(B, C, H, W, generator=g)
+
+
+def item_of(case, b, c, e):
+    """Work item that reads element e of plane (b, c): (c * B + b) * nseg + e / 4096."""
+    return (c * case[0] + b) * prepass_regime(case)["nseg"] + e // PRE_SEG
+
+
+def emulate_gb(gp):
+    """The bias gradient in the summation order the header of csrc/conv_grad.hip states, in fp32 on the CPU (every torch
+    add below is one IEEE fp32 addition per element): thread t of 256 adds its 16 elements (k * 256 + t) * 4 + j of a
+    4096-element segment, k then j ascending, from 0.0f (elements past the plane are 0.0f); the 64 lanes of a wave fold by
+    xor 32, 16, ..., 1; the waves combine as (w0 + w1) + (w2 + w3); the finish adds a channel's B * nseg items in
+    ascending (batch, segment) from 0.0f."""
+    B, C, H, W = gp.shape
+    HW = H * W
+    nseg = -(-HW // PRE_SEG)
+    v = F.pad(gp.reshape(B, C, HW).float(), (0, nseg * PRE_SEG - HW)).reshape(B, C, nseg, PRE_SEG // 1024, 256, 4)
+    t = torch.zeros(B, C, nseg, 256)
+    for k in range(PRE_SEG // 1024):
+        for j in range(4):
+            t = t + v[:, :, :, k, :, j]
+    t = t.reshape(B, C, nseg, 4, 64)
+    lanes = torch.arange(64)
+    for d in (32, 16, 8, 4, 2, 1):
+        t = t + t[..., lanes ^ d]
+    w = t[..., 0]                                   # (B, C, nseg, 4): every lane holds the wave's sum
+    items = (w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])
+    gb = torch.zeros(C)
+    for b in range(B):
+        for s in range(nseg):
+            gb = gb + items[b, :, s]
+    return gb

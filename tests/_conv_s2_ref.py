@@ -7,7 +7,7 @@ gradient's plan restated, the cases and the bounds.  The bounds are those of _co
   gx   max|got - exact| <= GX_BOUND (5e-6) * max|exact|
   gw   (a) the same 5e-6;  (b) |got - exact| <= (3 * 2^-22 + gamma_n) * sum|g'||x| elementwise, n = B*Ho*Wo.
 
-Every case keeps n <= 1105, so (b) stays discriminating (gamma_1105 = 6.6e-5 against a dropped term's 1 / sqrt(n) = 3e-2).
+Every case of CASES keeps n <= 1105, so (b) stays discriminating (gamma_1105 = 6.6e-5 against a dropped term's 1 / sqrt(n) = 3e-2).
 The emulations take mutants (a dropped parity, a dropped tap, a lost last odd row or column, a lost slice): what
 test_host_conv_s2_ref.py shows the bounds to catch.
 """
@@ -67,6 +67,37 @@ def masked(case, m=0):
     """g' = (y > 0) ? gy * 2^m : 0 of the case -- exact in fp32."""
     _, _, _, gy, y = inputs(case)
     return R.mask(gy * 2.0 ** m, y)
+
+
+#: (B, H, W, k, Cin, Cout) that take dkt_conv2d_wgrad_s2 (and the finishing kernel) out of "one item per block, T = 512":
+#: the regimes of _conv_wgrad_ref.PLAN_CASES on the Ho x Wo grid
+PLAN_CASES = [
+    (2, 83, 512, 3, 260, 257),   # grid 42 x 256: T = 2048, k = 3, walked (300 items), odd H, channel tails on both sides
+    (3, 79, 512, 1, 70, 520),    # grid 40 x 256: T = 2048, k = 1, walked (270 items), odd H
+    (3, 291, 48, 3, 257, 257),   # grid 146 x 24: T = 1024, one column tile, bands of 21 and 10 tiles, 300 items
+    (2, 127, 511, 3, 130, 70),   # grid 64 x 256: T = 512, walked (384 items), odd H and W, channel tails
+    (1, 12, 16, 3, 384, 320),    # grid 6 x 8, 1 105 920 weights: the finishing kernel strides
+]
+PLAN_IDS = ["x".join(str(v) for v in c) for c in PLAN_CASES]
+WALKED = PLAN_CASES[:4]
+MIXED = PLAN_CASES[2]
+
+
+def plan_inputs(case):
+    """_conv_wgrad_ref.drawn_inputs at stride 2: x, weight, bias, upstream gradient, saved output."""
+    return WR.drawn_inputs(case, 2)
+
+
+def plan_masked(case):
+    """g' of a plan or drawn case: the upstream gradient behind the random mask."""
+    _, _, _, gy, y = plan_inputs(case)
+    return R.mask(gy, y)
+
+
+def regime_of(case):
+    """_conv_wgrad_ref.regime of dkt_conv2d_wgrad_s2 for the case (grid Ho x Wo)."""
+    B, H, W, k, cin, cout = case
+    return WR.regime(B, *out_size(H, W), cin, cout)
 
 
 def plan(case):

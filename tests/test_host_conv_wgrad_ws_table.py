@@ -5,7 +5,10 @@ dkt_conv2d_wgrad_s2_ws_floats returned when each file still had a plan of its ow
 
 Every fixed case of the two references has fewer than 256 work items at every slice size, so their rows see the plan's lower
 limit (512 pixels) but neither where it starts (2048) nor where it stops halving (256 items); the training-recipe shapes
-below them do, on both grids, and a plan that took rows for columns would change their rows."""
+below them do, on both grids, and a plan that took rows for columns would change their rows.  Those rows pin SIZES only.  The
+arithmetic at a plan that stops at 2048 or 1024 pixels, or has more items than blocks, is held on the device by
+test_gpu_conv_grad_plans.py on PLAN_CASES of the two references (test_host_conv_grad_plans.py asserts their regimes); their
+rows, recorded from the library before those tests existed (commit 7d30439), close the table."""
 import _conv_s2_ref as S
 import _conv_wgrad_ref as WR
 
@@ -35,11 +38,22 @@ TABLE = {
     (2, 160, 360, 1, 96, 128): (983040, 983040),
     (2, 80, 180, 3, 128, 128): (11796480, 2949120),
     (2, 240, 448, 3, 384, 256): (106168320, 26542080),
+    # PLAN_CASES of _conv_wgrad_ref.py, then of _conv_s2_ref.py (at 7d30439)
+    (2, 42, 256, 3, 260, 257): (7216560, 7216560),
+    (3, 88, 256, 1, 200, 250): (1650000, 900000),
+    (3, 146, 24, 3, 257, 257): (7133292, 3566646),
+    (2, 64, 255, 3, 130, 70): (5241600, 1310400),
+    (1, 6, 8, 3, 384, 320): (1105920, 1105920),
+    (2, 83, 512, 3, 260, 257): (25257960, 7216560),
+    (3, 79, 512, 1, 70, 520): (2184000, 546000),
+    (3, 291, 48, 3, 257, 257): (12483261, 7133292),
+    (2, 127, 511, 3, 130, 70): (5241600, 5241600),
+    (1, 12, 16, 3, 384, 320): (1105920, 1105920),
 }
 
 
 def test_the_table_covers_both_references_cases():
-    assert set(WR.CASES) | set(S.CASES) <= set(TABLE)
+    assert set(WR.CASES) | set(S.CASES) | set(WR.PLAN_CASES) | set(S.PLAN_CASES) <= set(TABLE)
 
 
 def test_workspace_sizes_are_the_recorded_ones():
