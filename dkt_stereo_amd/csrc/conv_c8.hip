@@ -15,19 +15,16 @@
 //     of conv2d.hip pull through L1 (and blocks are twice as large, so half as many of them stream the image).
 //   * ONE raw s_barrier per step, counted vmcnt AND counted lgkmcnt, no drained waits: DMA and fragment reads stay
 //     in flight across barriers.  Fragment registers are single-buffered: every fragment is re-read into its own
-//     register as soon as its last MFMA of the step has issued, one read per MFMA issue shadow (see C8_STEP).
+//     register as soon as its last MFMA of the step has issued, one read per MFMA issue shadow (see C8_STEP3, c8_pipe.h).
 //   * wave tile 64 co x NF rows x 32 columns (NF = 4: 128 accumulators); steps walk the taps column by column so that
 //     a B fragment (one patch row) serves three steps: 24 MFMAs per 8 fragment reads.
 //
 // Outputs: fp32 NCHW and / or C8S (the next convolution's operand), fused ConvGRU gate epilogues as conv2d.hip.
 #include "dkt_common.h"
+#include "c8_pipe.h"
 #include <cstdlib>
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 #define C8_MAX_SRC 4
-#define C8_PC 34                 // patch columns: 32 + halo
 
 struct C8Args {
     const char *src[C8_MAX_SRC];      // C8S tensors (all with the same Hp, Wp)
@@ -66,38 +63,6 @@ struct C8ArgsPair {
     C8Args p[2];
 };
 
-__device__ __forceinline__ float c8_sigmoid(float x) { return __frcp_rn(1.0f + __expf(-x)); }
-__device__ __forceinline__ float c8_tanh(float x) {
-    const float xc = x < -15.0f ? -15.0f : (x > 15.0f ? 15.0f : x);      // NaN passes through
-    const float t = __expf(2.0f * xc);
-    return (t - 1.0f) * __frcp_rn(t + 1.0f);
-}
-__device__ __forceinline__ unsigned c8_pack_h2(_Float16 a, _Float16 b) {
-    union { _Float16 h[2]; unsigned u; } v;
-    v.h[0] = a;
-    v.h[1] = b;
-    return v.u;
-}
-
-template <int N>
-__device__ __forceinline__ void c8_wait_vm() {
-    // vmcnt(N) only (expcnt / lgkmcnt fields at their no-wait maxima).  The builtin, not inline asm: hipcc keeps its own
-    // LDS-read bookkeeping across it, so the first pass after the barrier waits for ITS fragments only (counted lgkmcnt)
-    static_assert(N < 64, "vmcnt immediate");
-    __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
-}
-
-// Fragment reads are inline asm with hand-counted lgkmcnt waits: hipcc answers every LDS read that is in flight
-// across the step's barrier with lgkmcnt(0) at the first MFMA behind it, which exposed the latency of the six reads
-// issued just before the barrier in EVERY step (ablation: 296 us with the reads, 200 us without, MFMAs alone 182 us).
-template <int OFF>
-__device__ __forceinline__ void c8_lds_read(f16x8 &dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-template <int N>
-__device__ __forceinline__ void c8_wait_lgkm() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
 // WM x WN waves along (output channels, rows); wave tile 64 co x NF rows x 32 columns.
 // RING = weight ring slots: step s computes from slot s % RING while the images of steps s+1 .. s+RING-1 are in the ring or
 // on their way (short steps -- small wave tiles -- need the deeper rings to cover the DMA latency).
@@ -110,7 +75,6 @@ __device__ __forceinline__ void c8_wait_lgkm() {
 template <int WM, int WN, int NF, int RING, int PASSES>
 __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0, const int nblocks, const int bid, char *const lds) {
     static_assert(PASSES >= 1 && PASSES <= 3, "passes");
-    constexpr int C8_RING = RING;
     constexpr int NW = WM * WN;
     constexpr int TR = WN * NF;                      // output rows per block
     constexpr int PR = TR + 2;
@@ -124,7 +88,7 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
     constexpr int WPI = (WM * 4) / NW;               // weight DMA pieces per wave and step
     static_assert((WM * 4) % NW == 0, "weight image must split evenly over the waves");
     constexpr int MF = 2;
-    char *const lds_act = lds;                       // act[2][ACT_BYTES] | wring[C8_RING][WSLOT]
+    char *const lds_act = lds;                       // act[2][ACT_BYTES] | wring[RING][WSLOT]
     char *const lds_w = lds + 2 * ACT_BYTES;
 
     const bool second = bid >= nb0;
@@ -151,18 +115,10 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
     int tile = bid - blk_first;       // (the XCD-aware order of the fused ConvGRU launch measured -0.6 % here: r05_cfg_variants.txt)
     decode(tile, h0, w0, co_blk, b);
 
-    // ---- activation DMA: piece p = j * NW + wave covers units u = 64 p + lane of the chunk image
-    //      [q = 2 kg + hl][patch pixel]; the source offset of a lane inside the chunk's 4 planes is fixed per tile.
+    // ---- activation DMA (c8_pipe.h): the source offset of a lane inside the chunk's 4 planes is fixed per tile.
     unsigned aoff_cur[NIA], aoff_nxt[NIA];
     auto tile_offsets = [&](int th0, int tw0, unsigned (&off)[NIA]) {
-#pragma unroll
-        for (int j = 0; j < NIA; ++j) {
-            int u = 64 * (j * NW + wave) + lane;
-            u = u < NU ? u : 0;                              // slack lanes of the last piece re-read unit 0 into slack LDS
-            const int q = u / NPP, pp = u - q * NPP;
-            const int pr = pp / C8_PC, pc = pp - pr * C8_PC;
-            off[j] = (unsigned)(q * a.plane_bytes + ((long)(th0 + pr) * a.Wp + (tw0 + pc)) * 16);
-        }
+        c8_tile_offsets<NW, NPP, NU>(a, wave, lane, th0, tw0, off);
     };
     auto chunk_base = [&](int tb, int chunk) -> const char * {       // wave-uniform
         int s = 0, c = chunk;
@@ -173,11 +129,7 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
         return a.src[s] + (long)tb * a.src_bs[s] + (long)c * 4 * a.plane_bytes;
     };
     auto issue_act = [&](const char *base, const unsigned (&off)[NIA], int buf) {
-        char *dst = lds_act + buf * ACT_BYTES;
-#pragma unroll
-        for (int j = 0; j < NIA; ++j)
-            __builtin_amdgcn_global_load_lds((const void *)(base + off[j]),
-                                             (__attribute__((address_space(3))) void *)(dst + min(j * NW + wave, NPR) * 1024), 16, 0, 0);
+        c8_issue_act<NW, NPR>(wave, base, off, lds_act + buf * ACT_BYTES);
     };
     // ---- weight DMA: the step image of this block's WM co64 blocks is contiguous (WM * 4 KB)
     // The images of consecutive steps of one tile are wstep bytes apart ((chunk, tap) is the outer index).
@@ -212,28 +164,27 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
     //                     B = act + ((2 kg + hl) * NPP + (wn*NF + n + dy) * 34 + li + dx) * 16
     const int a_lane = wm * 4096 + kg * 1024 + li * 16;
     const int b_lane = (2 * kg * NPP + wn * NF * C8_PC + li) * 16;
-    f16x8 Ahi[MF], Alo[MF], Bhi[NF + 2], Blo[NF + 2];      // B: one fragment per patch ROW of the current tap column (see C8_STEP)
+    f16x8 Ahi[MF], Alo[MF], Bhi[NF + 2], Blo[NF + 2];      // B: one fragment per patch ROW of the current tap column (see C8_STEP3, c8_pipe.h)
     const unsigned lds_w_addr = (unsigned)(size_t)(__attribute__((address_space(3))) char *)lds_w + a_lane;
     const unsigned lds_b_addr = (unsigned)(size_t)(__attribute__((address_space(3))) char *)lds_act + b_lane;
-    // One MFMA / one fragment read, each pinned in program order: the step below places at most one LDS read in the
-    // issue shadow of each MFMA (clusters of six reads between passes cost ~90 us of the 290 on the 384 -> 256 layer --
-    // not their waits, their issue).  Offsets must be literals for the asm immediates: macros, not loops.
-#define C8_MM(A, m, B, r, n)                                                                       \
-    {                                                                                              \
-        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[m], B[r], acc[m][n], 0, 0, 0);        \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-    }
-#define C8_RD(dst, off, addr)                                  \
-    {                                                          \
-        c8_lds_read<(off)>(dst, addr);                         \
-        __builtin_amdgcn_sched_barrier(0);                     \
-    }
-#define C8_RDL(dst, off, addr)                                            \
-    {                                                                     \
-        c8_lds_read<(off)>(dst, addr);                                    \
-        __builtin_amdgcn_sched_barrier(0);                                \
-    }
-#define C8_ROW(r, dx, plane) ((plane) + ((r) * C8_PC + (dx)) * 16)      /* fragment of patch row r at tap column dx */
+    // The (chunk, tap) steps are c8_pipe.h's, with both 32-channel blocks of the wave (MFP = MF = 2); what this kernel supplies:
+#define C8_ACC(m, n) acc[m][n]
+#define C8_WBASE lds_w_addr
+    // the weights of step s+1 (issued RING-2 steps ago) and, from step 6 on, the following chunk's patch
+    // have landed once at most the pieces issued after them are outstanding
+#define C8_WAIT_DMA(T)                                                                                                 \
+        if ((T) >= 1 && (T) <= RING - 3) c8_wait_vm<(RING - 3) * WPI + NIA>();                                         \
+        else c8_wait_vm<(RING - 3) * WPI>();
+    // the image of step s+RING-1 into the slot of step s-1 (all of its reads were consumed before this step's barrier);
+    // at the chunk's first step also the following chunk's patch
+#define C8_ISSUE_DMA(T)                                                                                                \
+        if ((T) == 10 - RING && !in_tile) wptr = w_next; /* the stream continues with the next tile's first image */  \
+        if ((T) == 0) { /* (before the weights: the patch must be older than every image the waits let fly) */        \
+            if (in_tile || !have_next) issue_act(act_f, aoff_cur, nxt);                                                \
+            else issue_act(act_f, aoff_nxt, nxt);                                                                      \
+        }                                                                                                              \
+        issue_w(wptr, sl2);                                                                                            \
+        wptr += wstep;
 
     // ------------------------------------------------------------------------------------------------
     // epilogue (after the tile's last step; the next tile's first DMA pieces are already in flight)
@@ -242,32 +193,16 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
     // (row n, column li) -- i.e. four groups j = r>>2 of four CONSECUTIVE channels.  fp32 tensors on the epilogue side
     // (gate operands, state, z) may therefore be kept in the "C4" layout [B][C/4][H][W][4]: one 16-byte access per
     // group instead of four strided 4-byte ones (a.f32_c4); NCHW remains for tensors other kernels read.
-    // C8S outputs need 8 consecutive channels per 16 bytes: a pair of groups (j, j+1) is completed by exchanging
-    // halves with lane ^ 32 (v_permlane32_swap), after which the lane stores group 2*jp + kg of its block.
+    // C8S outputs: c8_split_pair completes a pair of groups (j, j+1) to 8 consecutive channels per 16 bytes, after which the
+    // lane stores group 2*jp + kg of its block.
     auto store_c8_pair = [&](char *dst_b, int ch_block, int g_end, int jp, int oh, int ow, bool inside, const float (&va)[4], const float (&vb)[4]) {
-        unsigned ha[2], la[2], hb[2], lb[2];
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            const float x0 = va[2 * d] * a.act_scale, x1 = va[2 * d + 1] * a.act_scale;
-            const float y0 = vb[2 * d] * a.act_scale, y1 = vb[2 * d + 1] * a.act_scale;
-            const _Float16 a0 = (_Float16)x0, a1 = (_Float16)x1, b0 = (_Float16)y0, b1 = (_Float16)y1;
-            ha[d] = c8_pack_h2(a0, a1);
-            la[d] = c8_pack_h2((_Float16)(x0 - (float)a0), (_Float16)(x1 - (float)a1));
-            hb[d] = c8_pack_h2(b0, b1);
-            lb[d] = c8_pack_h2((_Float16)(y0 - (float)b0), (_Float16)(y1 - (float)b1));
-        }
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            auto r = __builtin_amdgcn_permlane32_swap(ha[d], hb[d], false, false);
-            ha[d] = r[0]; hb[d] = r[1];
-            auto q = __builtin_amdgcn_permlane32_swap(la[d], lb[d], false, false);
-            la[d] = q[0]; lb[d] = q[1];
-        }
+        u32x4 hi, lo;
+        c8_split_pair(va, vb, a.act_scale, hi, lo);
         const int g = (ch_block >> 3) + 2 * jp + kg;
         if (inside && g < g_end) {            // (groups past the destination's padded channel count do not exist)
             char *p = dst_b + (long)g * 2 * a.out_c8_plane + ((long)(oh + 1) * a.out_c8_Wp + (ow + 1)) * 16;
-            *(uint4 *)p = make_uint4(ha[0], ha[1], hb[0], hb[1]);
-            *(uint4 *)(p + a.out_c8_plane) = make_uint4(la[0], la[1], lb[0], lb[1]);
+            *(u32x4 *)p = hi;
+            *(u32x4 *)(p + a.out_c8_plane) = lo;
         }
     };
     // address of the 4 channels [c4, c4+4) of pixel px in an fp32 tensor (batch base already applied)
@@ -291,7 +226,7 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
                 if (i < nvalid) p[(long)i * iHW] = v[i];
         }
     };
-    char *const lds_head = lds + 2 * ACT_BYTES + C8_RING * WSLOT;      // epi 3 only: [wave][NF][9][32] floats
+    char *const lds_head = lds + 2 * ACT_BYTES + RING * WSLOT;      // epi 3 only: [wave][NF][9][32] floats
     auto epilogue_head = [&]() {
         const int co_w = co_blk + wm * 64;
         const bool idle = co_w >= a.n_co64 * 64;
@@ -472,37 +407,16 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
     issue_act(chunk_base(b, 0), aoff_cur, 0);
     const char *wptr = w_tile(co_blk);          // image of the next step to fetch
 #pragma unroll
-    for (int s = 0; s < C8_RING - 1; ++s) {
+    for (int s = 0; s < RING - 1; ++s) {
         issue_w(wptr, s);
         wptr += wstep;
     }
     c8_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
-    // fragments of step 0 that the steps do not fetch themselves: Alo, rows 0 .. NF-1 (in the order the waits count).
-    // PASSES == 1 keeps the A fragments double-buffered in the registers the other forms call Ahi / Alo: a chunk has nine steps,
-    // so a tile's even chunks start from Ahi and its odd ones from Alo -- the chunk loop runs two chunks per trip (the host
-    // refuses odd chunk counts at one pass; a run-time choice between the two step sequences sent the accumulators to scratch).
-    // C8_PRIME(g_) fetches the first step's fragments of a tile from ring slot `sl` / activation buffer g_ & 1.
-#define C8_PRIME(g_)                                                                                        \
-    {                                                                                                       \
-        const unsigned aw = lds_w_addr + sl * WSLOT, ab = lds_b_addr + ((g_) & 1) * ACT_BYTES;              \
-        if constexpr (PASSES == 1) { C8_RD(Ahi[0], 0, aw) C8_RD(Ahi[1], 512, aw) }                         \
-        else { C8_RD(Alo[0], 2048, aw) C8_RD(Alo[1], 2048 + 512, aw) }                                      \
-        C8_RD(Bhi[0], C8_ROW(0, 0, 0), ab)                                                                  \
-        if constexpr (NF > 1) C8_RD(Bhi[1], C8_ROW(1, 0, 0), ab)                                            \
-        if constexpr (NF > 2) C8_RD(Bhi[2], C8_ROW(2, 0, 0), ab)                                            \
-        if constexpr (NF > 3) C8_RD(Bhi[3], C8_ROW(3, 0, 0), ab)                                            \
-        if constexpr (PASSES == 3) {                                                                        \
-            C8_RDL(Blo[0], C8_ROW(0, 0, NPP * 16), ab)                                                      \
-            if constexpr (NF > 1) C8_RDL(Blo[1], C8_ROW(1, 0, NPP * 16), ab)                                \
-            if constexpr (NF > 2) C8_RDL(Blo[2], C8_ROW(2, 0, NPP * 16), ab)                                \
-            if constexpr (NF > 3) C8_RDL(Blo[3], C8_ROW(3, 0, NPP * 16), ab)                                \
-        }                                                                                                   \
-        c8_wait_lgkm<0>();                                                                                  \
-    }
+    // the fragments of step 0 that the steps do not fetch themselves (C8_FIRST_FRAGS, c8_pipe.h)
     int g = 0;              // chunks consumed by this block: activation buffer parity
     int sl = 0;             // ring slot of the step being computed
-    C8_PRIME(0)
+    C8_FIRST_FRAGS(MF, 0)
     for (;;) {
         const int tn = tile + blk_count;
         const bool have_next = tn < a.total_tiles;
@@ -518,175 +432,17 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
             if (!in_tile && have_next) tile_offsets(nh0, nw0, aoff_nxt);                                          \
             const char *act_f = chunk_base(b_f, c_f);                                                             \
             const int cur = g & 1, nxt = cur ^ 1;
-            // One (chunk, tap) step.  Steps run tap COLUMN by column (dx outer, dy inner: the weight images are packed in
-            // that order), so that a B fragment -- one patch row r at column dx -- serves the (up to) three steps dy = r - n:
-            // step (dx, dy) multiplies row n + dy for its output row n.  Rows are re-read into their own registers when
-            // they die: row 0 after step dy = 0, row 1 after dy = 1, rows 2 .. NF-1 during dy = 2 (each after the MFMAs of
-            // n = r - 2), always for the NEXT column (or the next chunk's column 0); rows NF and NF+1, first needed at
-            // dy = 1 / dy = 2, are fetched one step ahead (during dy = 0 / dy = 1 of their own column).  8 reads per step for
-            // the 64 x 4-row wave tile instead of 12: the convolution's time follows its LDS read volume (ablation: 278 us
-            // at 12 reads per step, 228 at 8, 208 at 0).  LDS reads in issue order (the waits count them):
-            //   X (Alo x Bhi): Ahi[0], Ahi[1]; dy = 0: row NF (hi, lo); dy = 1: row NF+1 (hi, lo)
-            //   Y (Ahi x Bhi): Alo'[0], Alo'[1], then the hi halves of the dying rows
-            //   Z (Ahi x Blo): the lo halves of the dying rows
-#define C8_STEP(T)                                                                                                     \
-    {                                                                                                                  \
-        constexpr int DX = (T) / 3, DY = (T) % 3, NDX = (DX + 1) % 3;                                                  \
-        const int sl1 = sl + 1 == C8_RING ? 0 : sl + 1, sl2 = sl == 0 ? C8_RING - 1 : sl - 1;                         \
-        const unsigned adw_s = lds_w_addr + sl * WSLOT;                                                                \
-        const unsigned adw_n = lds_w_addr + sl1 * WSLOT;                                                               \
-        const unsigned adb_c = lds_b_addr + cur * ACT_BYTES;                     /* this column's patch */             \
-        const unsigned adb_n = lds_b_addr + (DX < 2 ? cur : nxt) * ACT_BYTES;    /* the next column's   */             \
-        /* the weights of step s+1 (issued RING-2 steps ago) and, from step 6 on, the following chunk's patch      */ \
-        /* have landed once at most the pieces issued after them are outstanding                                   */ \
-        if ((T) >= 1 && (T) <= C8_RING - 3) c8_wait_vm<(C8_RING - 3) * WPI + NIA>();                                   \
-        else c8_wait_vm<(C8_RING - 3) * WPI>();                                                                        \
-        __builtin_amdgcn_s_barrier();                                                                                  \
-        /* Alo and this step's hi rows are in; what the previous step read after them may still fly */                \
-        if constexpr (DY == 0) c8_wait_lgkm<(NF > 2 ? NF - 2 : 0)>();                                                  \
-        else if constexpr (DY == 1) c8_wait_lgkm<2>();                                                                 \
-        else c8_wait_lgkm<(NF > 1 ? 2 : 0)>();                                                                         \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        /* ---- X */                                                                                                   \
-        C8_MM(Alo, 0, Bhi, DY, 0) C8_RD(Ahi[0], 0, adw_s)                                                                 \
-        C8_MM(Alo, 1, Bhi, DY, 0) C8_RD(Ahi[1], 512, adw_s)                                                               \
-        if constexpr (NF > 1) { C8_MM(Alo, 0, Bhi, 1 + DY, 1)                                                             \
-            if constexpr (DY < 2) C8_RD(Bhi[NF + DY], C8_ROW(NF + DY, DX, 0), adb_c)                                   \
-            C8_MM(Alo, 1, Bhi, 1 + DY, 1)                                                                                 \
-            if constexpr (DY < 2) C8_RDL(Blo[NF + DY], C8_ROW(NF + DY, DX, NPP * 16), adb_c) }                         \
-        else if constexpr (DY < 2) { C8_RD(Bhi[NF + DY], C8_ROW(NF + DY, DX, 0), adb_c)                                \
-            C8_RDL(Blo[NF + DY], C8_ROW(NF + DY, DX, NPP * 16), adb_c) }                                               \
-        if constexpr (NF > 2) { C8_MM(Alo, 0, Bhi, 2 + DY, 2) C8_MM(Alo, 1, Bhi, 2 + DY, 2) }                                \
-        if constexpr (NF > 3) { C8_MM(Alo, 0, Bhi, 3 + DY, 3) C8_MM(Alo, 1, Bhi, 3 + DY, 3) }                                \
-        /* ---- DMA issue: the image of step s+RING-1 into the slot of step s-1 (all of its reads were consumed       */ \
-        /* before this step's barrier); at the chunk's first step also the following chunk's patch                   */ \
-        if ((T) == 10 - C8_RING && !in_tile) wptr = w_next; /* the stream continues with the next tile's first image */ \
-        if ((T) == 0) { /* (before the weights: the patch must be older than every image the waits let fly) */        \
-            if (in_tile || !have_next) issue_act(act_f, aoff_cur, nxt);                                                \
-            else issue_act(act_f, aoff_nxt, nxt);                                                                      \
-        }                                                                                                              \
-        issue_w(wptr, sl2);                                                                                            \
-        wptr += wstep;                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        c8_wait_lgkm<(DY < 2 ? 2 : 0)>(); /* Ahi is in (the row read ahead may still fly) */                           \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        /* ---- Y */                                                                                                   \
-        C8_MM(Ahi, 0, Bhi, DY, 0) C8_RD(Alo[0], 2048, adw_n)                                                              \
-        C8_MM(Ahi, 1, Bhi, DY, 0) C8_RD(Alo[1], 2048 + 512, adw_n)                                                        \
-        if constexpr (DY == 0) C8_RD(Bhi[0], C8_ROW(0, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 1 && NF > 1) C8_RD(Bhi[1], C8_ROW(1, NDX, 0), adb_n)                                       \
-        if constexpr (DY == 2 && NF > 2) C8_RD(Bhi[2], C8_ROW(2, NDX, 0), adb_n)                                       \
-        if constexpr (NF > 1) { C8_MM(Ahi, 0, Bhi, 1 + DY, 1) C8_MM(Ahi, 1, Bhi, 1 + DY, 1)                                  \
-            if constexpr (DY == 2 && NF > 3) C8_RD(Bhi[3], C8_ROW(3, NDX, 0), adb_n) }                                 \
-        if constexpr (NF > 2) { C8_MM(Ahi, 0, Bhi, 2 + DY, 2) C8_MM(Ahi, 1, Bhi, 2 + DY, 2) }                                \
-        if constexpr (NF > 3) { C8_MM(Ahi, 0, Bhi, 3 + DY, 3) C8_MM(Ahi, 1, Bhi, 3 + DY, 3) }                                \
-        /* ---- Z (every lo row of this step was read before this step's X reads: in since the wait before Y) */       \
-        C8_MM(Ahi, 0, Blo, DY, 0) C8_MM(Ahi, 1, Blo, DY, 0)                                                                  \
-        if constexpr (DY == 0) C8_RDL(Blo[0], C8_ROW(0, NDX, NPP * 16), adb_n)                                         \
-        if constexpr (DY == 1 && NF > 1) C8_RDL(Blo[1], C8_ROW(1, NDX, NPP * 16), adb_n)                               \
-        if constexpr (DY == 2 && NF > 2) C8_RDL(Blo[2], C8_ROW(2, NDX, NPP * 16), adb_n)                               \
-        if constexpr (NF > 1) { C8_MM(Ahi, 0, Blo, 1 + DY, 1) C8_MM(Ahi, 1, Blo, 1 + DY, 1)                                  \
-            if constexpr (DY == 2 && NF > 3) C8_RDL(Blo[3], C8_ROW(3, NDX, NPP * 16), adb_n) }                         \
-        if constexpr (NF > 2) { C8_MM(Ahi, 0, Blo, 2 + DY, 2) C8_MM(Ahi, 1, Blo, 2 + DY, 2) }                                \
-        if constexpr (NF > 3) { C8_MM(Ahi, 0, Blo, 3 + DY, 3) C8_MM(Ahi, 1, Blo, 3 + DY, 3) }                                \
-        sl = sl1;                                                                                                      \
-    }
-            // ---- the step's shared head (waits for this step's DMA, barrier) and DMA issue, as in C8_STEP
-#define C8_STEP_HEAD(T)                                                                                                \
-        constexpr int DX = (T) / 3, DY = (T) % 3, NDX = (DX + 1) % 3;                                                  \
-        const int sl1 = sl + 1 == C8_RING ? 0 : sl + 1, sl2 = sl == 0 ? C8_RING - 1 : sl - 1;                         \
-        const unsigned adw_s = lds_w_addr + sl * WSLOT;                                                                \
-        const unsigned adw_n = lds_w_addr + sl1 * WSLOT;                                                               \
-        const unsigned adb_c = lds_b_addr + cur * ACT_BYTES;                                                           \
-        const unsigned adb_n = lds_b_addr + (DX < 2 ? cur : nxt) * ACT_BYTES;                                          \
-        (void)adw_s; (void)adw_n; (void)adb_c; (void)adb_n;                                                            \
-        if ((T) >= 1 && (T) <= C8_RING - 3) c8_wait_vm<(C8_RING - 3) * WPI + NIA>();                                   \
-        else c8_wait_vm<(C8_RING - 3) * WPI>();                                                                        \
-        __builtin_amdgcn_s_barrier();
-#define C8_STEP_DMA(T)                                                                                                 \
-        if ((T) == 10 - C8_RING && !in_tile) wptr = w_next;                                                            \
-        if ((T) == 0) {                                                                                                \
-            if (in_tile || !have_next) issue_act(act_f, aoff_cur, nxt);                                                \
-            else issue_act(act_f, aoff_nxt, nxt);                                                                      \
-        }                                                                                                              \
-        issue_w(wptr, sl2);                                                                                            \
-        wptr += wstep;                                                                                                 \
-        __builtin_amdgcn_sched_barrier(0);
-            // PASSES == 2: C8_STEP without its Z pass and without any lo row.  LDS reads in issue order:
-            //   X (Alo x Bhi): Ahi[0], Ahi[1]; dy = 0: row NF; dy = 1: row NF+1
-            //   Y (Ahi x Bhi): Alo'[0], Alo'[1], then the dying rows (for the next column)
-            // so a step starts with its Alo and rows in once at most the previous step's dying-row reads fly (1 after dy = 0,
-            // 1 after dy = 1 when NF > 1, none after dy = 2: the rows re-read there are this step's)
-#define C8_STEP2(T)                                                                                                    \
-    {                                                                                                                  \
-        C8_STEP_HEAD(T)                                                                                                \
-        if constexpr (DY == 1) c8_wait_lgkm<1>();                                                                      \
-        else if constexpr (DY == 2) c8_wait_lgkm<(NF > 1 ? 1 : 0)>();                                                  \
-        else c8_wait_lgkm<0>();                                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        C8_MM(Alo, 0, Bhi, DY, 0) C8_RD(Ahi[0], 0, adw_s)                                                              \
-        C8_MM(Alo, 1, Bhi, DY, 0) C8_RD(Ahi[1], 512, adw_s)                                                            \
-        if constexpr (NF > 1) { C8_MM(Alo, 0, Bhi, 1 + DY, 1)                                                          \
-            if constexpr (DY < 2) C8_RD(Bhi[NF + DY], C8_ROW(NF + DY, DX, 0), adb_c)                                   \
-            C8_MM(Alo, 1, Bhi, 1 + DY, 1) }                                                                            \
-        else if constexpr (DY < 2) C8_RD(Bhi[NF + DY], C8_ROW(NF + DY, DX, 0), adb_c)                                  \
-        if constexpr (NF > 2) { C8_MM(Alo, 0, Bhi, 2 + DY, 2) C8_MM(Alo, 1, Bhi, 2 + DY, 2) }                          \
-        if constexpr (NF > 3) { C8_MM(Alo, 0, Bhi, 3 + DY, 3) C8_MM(Alo, 1, Bhi, 3 + DY, 3) }                          \
-        C8_STEP_DMA(T)                                                                                                 \
-        c8_wait_lgkm<(DY < 2 ? 1 : 0)>(); /* Ahi is in (the row read ahead may still fly) */                           \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        C8_MM(Ahi, 0, Bhi, DY, 0) C8_RD(Alo[0], 2048, adw_n)                                                           \
-        C8_MM(Ahi, 1, Bhi, DY, 0) C8_RD(Alo[1], 2048 + 512, adw_n)                                                     \
-        if constexpr (DY == 0) C8_RD(Bhi[0], C8_ROW(0, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 1 && NF > 1) C8_RD(Bhi[1], C8_ROW(1, NDX, 0), adb_n)                                       \
-        if constexpr (DY == 2 && NF > 2) C8_RD(Bhi[2], C8_ROW(2, NDX, 0), adb_n)                                       \
-        if constexpr (NF > 1) { C8_MM(Ahi, 0, Bhi, 1 + DY, 1) C8_MM(Ahi, 1, Bhi, 1 + DY, 1)                            \
-            if constexpr (DY == 2 && NF > 3) C8_RD(Bhi[3], C8_ROW(3, NDX, 0), adb_n) }                                 \
-        if constexpr (NF > 2) { C8_MM(Ahi, 0, Bhi, 2 + DY, 2) C8_MM(Ahi, 1, Bhi, 2 + DY, 2) }                          \
-        if constexpr (NF > 3) { C8_MM(Ahi, 0, Bhi, 3 + DY, 3) C8_MM(Ahi, 1, Bhi, 3 + DY, 3) }                          \
-        sl = sl1;                                                                                                      \
-    }
-            // PASSES == 1: one product per block, A fragments double-buffered (PA: this step's, PB: the next step's, fetched first
-            // thing behind the barrier), MFMAs row by row so that a dying row is re-read as soon as its last product has issued.
-            // LDS reads in issue order: PB[0], PB[1]; dy < 2: row NF + dy; then the dying rows.  Waits as in C8_STEP2.
-#define C8_STEP1(T, PA, PB)                                                                                            \
-    {                                                                                                                  \
-        C8_STEP_HEAD(T)                                                                                                \
-        if constexpr (DY == 1) c8_wait_lgkm<1>();                                                                      \
-        else if constexpr (DY == 2) c8_wait_lgkm<(NF > 1 ? 1 : 0)>();                                                  \
-        else c8_wait_lgkm<0>();                                                                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        C8_RD(PB[0], 0, adw_n) C8_RD(PB[1], 512, adw_n)                                                                \
-        if constexpr (DY < 2) C8_RD(Bhi[NF + DY], C8_ROW(NF + DY, DX, 0), adb_c)                                       \
-        C8_MM(PA, 0, Bhi, DY, 0) C8_MM(PA, 1, Bhi, DY, 0)                                                              \
-        if constexpr (DY == 0) C8_RD(Bhi[0], C8_ROW(0, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 1 && NF > 1) C8_RD(Bhi[1], C8_ROW(1, NDX, 0), adb_n)                                       \
-        if constexpr (DY == 2 && NF > 2) C8_RD(Bhi[2], C8_ROW(2, NDX, 0), adb_n)                                       \
-        C8_STEP_DMA(T)                                                                                                 \
-        if constexpr (NF > 1) { C8_MM(PA, 0, Bhi, 1 + DY, 1) C8_MM(PA, 1, Bhi, 1 + DY, 1)                              \
-            if constexpr (DY == 2 && NF > 3) C8_RD(Bhi[3], C8_ROW(3, NDX, 0), adb_n) }                                 \
-        if constexpr (NF > 2) { C8_MM(PA, 0, Bhi, 2 + DY, 2) C8_MM(PA, 1, Bhi, 2 + DY, 2) }                            \
-        if constexpr (NF > 3) { C8_MM(PA, 0, Bhi, 3 + DY, 3) C8_MM(PA, 1, Bhi, 3 + DY, 3) }                            \
-        sl = sl1;                                                                                                      \
-    }
-#define C8_CHUNK1(PA, PB)                                                                                     \
-            C8_STEP1(0, PA, PB) C8_STEP1(1, PB, PA) C8_STEP1(2, PA, PB) C8_STEP1(3, PB, PA) C8_STEP1(4, PA, PB)   \
-            C8_STEP1(5, PB, PA) C8_STEP1(6, PA, PB) C8_STEP1(7, PB, PA) C8_STEP1(8, PA, PB)
         if constexpr (PASSES == 1) {
             for (int c = 0; c < a.nchunks; c += 2) {
-                { C8_CHUNK_SETUP(c) C8_CHUNK1(Ahi, Alo) }
+                { C8_CHUNK_SETUP(c) C8_CHUNK1(MF, Ahi, Alo) }
                 ++g;
-                { C8_CHUNK_SETUP(c + 1) C8_CHUNK1(Alo, Ahi) }
+                { C8_CHUNK_SETUP(c + 1) C8_CHUNK1(MF, Alo, Ahi) }
                 ++g;
             }
         } else {
             for (int c = 0; c < a.nchunks; ++c, ++g) {
                 C8_CHUNK_SETUP(c)
-                if constexpr (PASSES == 3) {
-                    C8_STEP(0) C8_STEP(1) C8_STEP(2) C8_STEP(3) C8_STEP(4) C8_STEP(5) C8_STEP(6) C8_STEP(7) C8_STEP(8)
-                } else {
-                    C8_STEP2(0) C8_STEP2(1) C8_STEP2(2) C8_STEP2(3) C8_STEP2(4) C8_STEP2(5) C8_STEP2(6) C8_STEP2(7) C8_STEP2(8)
-                }
+                C8_CHUNK(MF)
             }
         }
         c8_wait_lgkm<0>();      // the prefetched fragments of the next tile have landed: their registers are stable
@@ -699,7 +455,7 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
         // The fragments the last step fetched for this tile's first step are fetched AGAIN here (their LDS images are
         // untouched: no DMA is issued during the epilogue): that makes the 16 + 8 NF fragment registers dead across the
         // epilogue, which needs them for its operand batches (see epilogue()).
-        C8_PRIME(g)
+        C8_FIRST_FRAGS(MF, g)
     }
     c8_wait_vm<0>();        // no DMA may land in this block's LDS after it has been released
 }

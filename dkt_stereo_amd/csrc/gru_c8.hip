@@ -18,21 +18,17 @@
 //   gate B   h' = (1 - z) h + z tanh(.) -> fp32 NCHW in place and the C8S twin in place (a neighbour can only have
 //            reached this point after it saw OUR flag, i.e. after we read every patch of the old state).
 //
-// The weight ring, the activation patches, the counted vmcnt / lgkmcnt waits and the fragment-read schedule are those of
-// conv_c8.hip's 256 co x 8 rows shape (WM 4 x WN 2 waves, NF 4, ring 4); phase B runs the same step with ONE 32-channel
-// block per wave (MF = 1) and 8 KB weight images in the same 16 KB ring slots.
+// The weight ring, the activation patches, the counted vmcnt / lgkmcnt waits and the fragment-read schedule are c8_pipe.h's,
+// the one copy conv_c8.hip expands too, at its 256 co x 8 rows shape (WM 4 x WN 2 waves, NF 4, ring 4); phase B runs the same
+// step with ONE 32-channel block per wave (MFP = 1) and 8 KB weight images in the same 16 KB ring slots.
 //
 // Residency: the grid never exceeds what the device holds (one block per CU), and a block's next tile is at least
 // tiles_w + 2 tiles ahead, so every flag a block waits for is produced by a tile some block has ALREADY started or will
 // start without waiting for us (no cycle).  Every spin is bounded; a timeout raises the error word.
 #include "dkt_common.h"
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "c8_pipe.h"
 
 #define G8_MAX_X 3
-#define G8_PC 34
 #define G8_SPIN_LIMIT (1u << 21)
 
 struct G8Args {
@@ -55,31 +51,6 @@ struct G8ArgsPair {
     unsigned *err;
 };
 
-__device__ __forceinline__ float g8_sigmoid(float x) { return __frcp_rn(1.0f + __expf(-x)); }
-__device__ __forceinline__ float g8_tanh(float x) {
-    const float xc = x < -15.0f ? -15.0f : (x > 15.0f ? 15.0f : x);      // NaN passes through
-    const float t = __expf(2.0f * xc);
-    return (t - 1.0f) * __frcp_rn(t + 1.0f);
-}
-__device__ __forceinline__ unsigned g8_pack_h2(_Float16 a, _Float16 b) {
-    union { _Float16 h[2]; unsigned u; } v;
-    v.h[0] = a;
-    v.h[1] = b;
-    return v.u;
-}
-template <int N>
-__device__ __forceinline__ void g8_wait_vm() {
-    static_assert(N < 64, "vmcnt immediate");
-    __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
-}
-template <int OFF>
-__device__ __forceinline__ void g8_lds_read(f16x8 &dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-template <int N>
-__device__ __forceinline__ void g8_wait_lgkm() {
-    asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory");
-}
 
 typedef __attribute__((address_space(1))) unsigned g8_gu32;
 
@@ -89,7 +60,7 @@ template <int PASSES>
 __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) {
     static_assert(PASSES >= 1 && PASSES <= 3, "passes");
     constexpr int NW = 8, WM = 4, NF = 4, TR = 8, PR = TR + 2;
-    constexpr int NPP = PR * G8_PC;                  // 340 patch pixels
+    constexpr int NPP = PR * C8_PC;                  // 340 patch pixels
     constexpr int NU = NPP * 4;                      // 16-byte units per chunk
     constexpr int NPR = (NU + 63) / 64;              // 22 one-KiB DMA pieces
     constexpr int NIA = (NPR + NW - 1) / NW;         // 3 per wave
@@ -118,17 +89,10 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
     int txy = tile - b * a.tiles_xy;
     int w0 = (txy % a.tiles_w) * 32, h0 = (txy / a.tiles_w) * TR;
 
-    // ---- activation DMA (as conv_c8.hip): piece p = j * NW + wave covers units u = 64 p + lane of the chunk image
+    // ---- activation DMA (c8_pipe.h)
     unsigned aoff_cur[NIA], aoff_nxt[NIA];
     auto tile_offsets = [&](int th0, int tw0, unsigned (&off)[NIA]) {
-#pragma unroll
-        for (int j = 0; j < NIA; ++j) {
-            int u = 64 * (j * NW + wave) + lane;
-            u = u < NU ? u : 0;
-            const int q = u / NPP, pp = u - q * NPP;
-            const int pr = pp / G8_PC, pc = pp - pr * G8_PC;
-            off[j] = (unsigned)(q * a.plane_bytes + ((long)(th0 + pr) * a.Wp + (tw0 + pc)) * 16);
-        }
+        c8_tile_offsets<NW, NPP, NU>(a, wave, lane, th0, tw0, off);
     };
     auto x_chunk = [&](int tb, int c) -> const char * {              // wave-uniform
         int s = 0;
@@ -145,11 +109,7 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
         return c < a.nxc ? x_chunk(tb, c) : a.rh + (long)tb * a.rh_bs + (long)(c - a.nxc) * 4 * a.plane_bytes;
     };
     auto issue_act = [&](const char *base, const unsigned (&off)[NIA], int buf) {
-        char *dst = lds_act + buf * ACT_BYTES;
-#pragma unroll
-        for (int j = 0; j < NIA; ++j)
-            __builtin_amdgcn_global_load_lds((const void *)(base + off[j]),
-                                             (__attribute__((address_space(3))) void *)(dst + min(j * NW + wave, NPR) * 1024), 16, 0, 0);
+        c8_issue_act<NW, NPR>(wave, base, off, lds_act + buf * ACT_BYTES);
     };
     // ---- weight DMA: a phase-A step image is 16 KB (two 1-KiB pieces per wave), a phase-B one 8 KB (one piece per wave)
     auto issue_wA = [&](const char *img, int slot) {
@@ -213,55 +173,25 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
     //                     B = act + ((2 kg + hl) * NPP + (wn*NF + n + dy) * 34 + li + dx) * 16
     const int a_laneA = wm * 4096 + kg * 1024 + li * 16;
     const int a_laneB = (wm >> 1) * 4096 + kg * 1024 + ((wm & 1) * 32 + li) * 16;
-    const int b_lane = (2 * kg * NPP + wn * NF * G8_PC + li) * 16;
+    const int b_lane = (2 * kg * NPP + wn * NF * C8_PC + li) * 16;
     f16x8 Ahi[2], Alo[2], Bhi[NF + 2], Blo[NF + 2];
     const unsigned lds_w_base = (unsigned)(size_t)(__attribute__((address_space(3))) char *)lds_w;
     const unsigned lds_wA = lds_w_base + a_laneA, lds_wB = lds_w_base + a_laneB;
     const unsigned lds_b_addr = (unsigned)(size_t)(__attribute__((address_space(3))) char *)lds_act + b_lane;
 
-#define G8_MM(A, m, B, r, n)                                                                  \
-    {                                                                                         \
-        acc[MFPV == 2 ? m : 1][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[m], B[r], acc[MFPV == 2 ? m : 1][n], 0, 0, 0); \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-    }
-#define G8_RD(dst, off, addr)                  \
-    {                                          \
-        g8_lds_read<(off)>(dst, addr);         \
-        __builtin_amdgcn_sched_barrier(0);     \
-    }
-#define G8_ROW(r, dx, plane) ((plane) + ((r) * G8_PC + (dx)) * 16)
-
-    // One (chunk, tap) step, conv_c8.hip's C8_STEP at NF = 4 with MFP = 2 (phase A) or 1 (phase B) channel blocks per wave.
-    // `last` (the phase's last chunk): from step 6 on the ring is fed with the NEXT phase's images (w_next, other piece
-    // count), so the waits of steps 7 and 8 count pieces of the other kind: vmcnt(1) is exact for B images and merely
-    // early for A ones.
-#define G8_STEP(T, MFP)                                                                                                \
-    {                                                                                                                  \
-        constexpr int DX = (T) / 3, DY = (T) % 3, NDX = (DX + 1) % 3;                                                  \
-        constexpr int WPI = (MFP), MFPV = (MFP);                                                                       \
-        const int sl1 = sl + 1 == RING ? 0 : sl + 1, sl2 = sl == 0 ? RING - 1 : sl - 1;                                \
-        const unsigned adw_s = (MFP == 2 ? lds_wA : lds_wB) + sl * WSLOT;                                              \
-        const unsigned adw_n = (MFP == 2 ? lds_wA : lds_wB) + sl1 * WSLOT;                                             \
-        const unsigned adb_c = lds_b_addr + cur * ACT_BYTES;                                                           \
-        const unsigned adb_n = lds_b_addr + (DX < 2 ? cur : nxt) * ACT_BYTES;                                          \
-        if ((T) == 1) g8_wait_vm<WPI + NIA>();                                                                         \
-        else if ((T) >= 7 && MFP == 2) { if (last) g8_wait_vm<1>(); else g8_wait_vm<2>(); }                            \
-        else g8_wait_vm<WPI>();                                                                                        \
-        __builtin_amdgcn_s_barrier();                                                                                  \
-        g8_wait_lgkm<2>();                                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        /* ---- X (Alo x Bhi) */                                                                                       \
-        G8_MM(Alo, 0, Bhi, DY, 0) G8_RD(Ahi[0], 0, adw_s)                                                              \
-        if constexpr (MFP == 2) { G8_MM(Alo, 1, Bhi, DY, 0) G8_RD(Ahi[1], 512, adw_s) }                                \
-        G8_MM(Alo, 0, Bhi, 1 + DY, 1)                                                                                  \
-        if constexpr (DY < 2) G8_RD(Bhi[NF + DY], G8_ROW(NF + DY, DX, 0), adb_c)                                       \
-        if constexpr (MFP == 2) G8_MM(Alo, 1, Bhi, 1 + DY, 1)                                                          \
-        if constexpr (MFP == 1) G8_MM(Alo, 0, Bhi, 2 + DY, 2)                                                          \
-        if constexpr (DY < 2) G8_RD(Blo[NF + DY], G8_ROW(NF + DY, DX, NPP * 16), adb_c)                                \
-        if constexpr (MFP == 2) { G8_MM(Alo, 0, Bhi, 2 + DY, 2) G8_MM(Alo, 1, Bhi, 2 + DY, 2) }                        \
-        G8_MM(Alo, 0, Bhi, 3 + DY, 3)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Alo, 1, Bhi, 3 + DY, 3)                                                          \
-        /* ---- DMA issue: the image of step s+3 into the slot of step s-1; at the chunk's first step the next patch */ \
+    // The (chunk, tap) steps are c8_pipe.h's, at NF = 4, ring 4, with MFP = 2 (phase A) or 1 (phase B) channel blocks per wave:
+    // phase B accumulates into block 1 and reads its A fragments from the 8 KB images' lane base.
+#define C8_ACC(m, n) acc[MFP == 2 ? m : 1][n]
+#define C8_WBASE (MFP == 2 ? lds_wA : lds_wB)
+    // A step image is MFP pieces per wave.  `last` (the phase's last chunk): from step 6 on the ring is fed with the NEXT
+    // phase's images (w_next, other piece count), so the waits of steps 7 and 8 count pieces of the other kind: vmcnt(1) is
+    // exact for B images and merely early for A ones.
+#define C8_WAIT_DMA(T)                                                                                                 \
+        if ((T) == 1) c8_wait_vm<MFP + NIA>();                                                                         \
+        else if ((T) >= 7 && MFP == 2) { if (last) c8_wait_vm<1>(); else c8_wait_vm<2>(); }                            \
+        else c8_wait_vm<MFP>();
+    // the image of step s+3 into the slot of step s-1; at the chunk's first step the next patch
+#define C8_ISSUE_DMA(T)                                                                                                \
         if ((T) == 6 && last) wptr = w_next;                                                                           \
         if ((T) == 0) { if (use_nxt_off) issue_act(act_f, aoff_nxt, nxt); else issue_act(act_f, aoff_cur, nxt); }      \
         if ((T) >= 6 && last) {                                                                                        \
@@ -270,176 +200,9 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
         } else {                                                                                                       \
             if constexpr (MFP == 2) { issue_wA(wptr, sl2); wptr += WSTEP_A; }                                          \
             else { issue_wB(wptr, sl2); wptr += WSTEP_B; }                                                             \
-        }                                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        g8_wait_lgkm<(DY < 2 ? 2 : 0)>();                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        /* ---- Y (Ahi x Bhi) */                                                                                       \
-        G8_MM(Ahi, 0, Bhi, DY, 0) G8_RD(Alo[0], 2048, adw_n)                                                           \
-        if constexpr (MFP == 2) { G8_MM(Ahi, 1, Bhi, DY, 0) G8_RD(Alo[1], 2048 + 512, adw_n) }                         \
-        if constexpr (MFP == 1) G8_MM(Ahi, 0, Bhi, 1 + DY, 1)                                                          \
-        if constexpr (DY == 0) G8_RD(Bhi[0], G8_ROW(0, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 1) G8_RD(Bhi[1], G8_ROW(1, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 2) G8_RD(Bhi[2], G8_ROW(2, NDX, 0), adb_n)                                                 \
-        if constexpr (MFP == 2) { G8_MM(Ahi, 0, Bhi, 1 + DY, 1) G8_MM(Ahi, 1, Bhi, 1 + DY, 1) }                        \
-        if constexpr (MFP == 1) G8_MM(Ahi, 0, Bhi, 2 + DY, 2)                                                          \
-        if constexpr (DY == 2) G8_RD(Bhi[3], G8_ROW(3, NDX, 0), adb_n)                                                 \
-        if constexpr (MFP == 2) { G8_MM(Ahi, 0, Bhi, 2 + DY, 2) G8_MM(Ahi, 1, Bhi, 2 + DY, 2) }                        \
-        G8_MM(Ahi, 0, Bhi, 3 + DY, 3)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Bhi, 3 + DY, 3)                                                          \
-        /* ---- Z (Ahi x Blo) */                                                                                       \
-        G8_MM(Ahi, 0, Blo, DY, 0)                                                                                      \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Blo, DY, 0)                                                              \
-        if constexpr (DY == 0) G8_RD(Blo[0], G8_ROW(0, NDX, NPP * 16), adb_n)                                          \
-        if constexpr (DY == 1) G8_RD(Blo[1], G8_ROW(1, NDX, NPP * 16), adb_n)                                          \
-        if constexpr (DY == 2) G8_RD(Blo[2], G8_ROW(2, NDX, NPP * 16), adb_n)                                          \
-        G8_MM(Ahi, 0, Blo, 1 + DY, 1)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Blo, 1 + DY, 1)                                                          \
-        if constexpr (DY == 2) G8_RD(Blo[3], G8_ROW(3, NDX, NPP * 16), adb_n)                                          \
-        G8_MM(Ahi, 0, Blo, 2 + DY, 2)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Blo, 2 + DY, 2)                                                          \
-        G8_MM(Ahi, 0, Blo, 3 + DY, 3)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Blo, 3 + DY, 3)                                                          \
-        sl = sl1;                                                                                                      \
-    }
-    // the fragments a phase's first step does not fetch itself (after the DMA of its first patch and image has landed).
-    // PASSES == 1 keeps the A fragments double-buffered in Ahi / Alo: a chunk has nine steps, so even chunks of a phase compute
-    // their first step from Ahi and odd ones from Alo -- the chunk loops run two chunks per trip (the host refuses odd chunk
-    // counts at one pass), because a run-time choice between the two step sequences sent the accumulators to scratch.
-#define G8_FIRST_FRAGS(MFP)                                                                              \
-    {                                                                                                    \
-        const unsigned aw = (MFP == 2 ? lds_wA : lds_wB) + sl * WSLOT, ab = lds_b_addr + (g & 1) * ACT_BYTES; \
-        if constexpr (PASSES == 1) {                                                                     \
-            G8_RD(Ahi[0], 0, aw) if constexpr (MFP == 2) G8_RD(Ahi[1], 512, aw)                          \
-        } else {                                                                                         \
-            G8_RD(Alo[0], 2048, aw)                                                                      \
-            if constexpr (MFP == 2) G8_RD(Alo[1], 2048 + 512, aw)                                        \
-        }                                                                                                \
-        G8_RD(Bhi[0], G8_ROW(0, 0, 0), ab) G8_RD(Bhi[1], G8_ROW(1, 0, 0), ab)                            \
-        G8_RD(Bhi[2], G8_ROW(2, 0, 0), ab) G8_RD(Bhi[3], G8_ROW(3, 0, 0), ab)                            \
-        if constexpr (PASSES == 3) {                                                                     \
-            G8_RD(Blo[0], G8_ROW(0, 0, NPP * 16), ab) G8_RD(Blo[1], G8_ROW(1, 0, NPP * 16), ab)          \
-            G8_RD(Blo[2], G8_ROW(2, 0, NPP * 16), ab) G8_RD(Blo[3], G8_ROW(3, 0, NPP * 16), ab)          \
-        }                                                                                                \
-        g8_wait_lgkm<0>();                                                                               \
-    }
-    // ---- reduced-pass steps (conv_c8.hip's C8_STEP2 / C8_STEP1 at NF = 4): same DMA stream and vmcnt waits as G8_STEP
-#define G8_STEP_HEAD(T, MFP)                                                                                           \
-        constexpr int DX = (T) / 3, DY = (T) % 3, NDX = (DX + 1) % 3;                                                  \
-        constexpr int WPI = (MFP), MFPV = (MFP);                                                                       \
-        const int sl1 = sl + 1 == RING ? 0 : sl + 1, sl2 = sl == 0 ? RING - 1 : sl - 1;                                \
-        const unsigned adw_s = (MFP == 2 ? lds_wA : lds_wB) + sl * WSLOT;                                              \
-        const unsigned adw_n = (MFP == 2 ? lds_wA : lds_wB) + sl1 * WSLOT;                                             \
-        const unsigned adb_c = lds_b_addr + cur * ACT_BYTES;                                                           \
-        const unsigned adb_n = lds_b_addr + (DX < 2 ? cur : nxt) * ACT_BYTES;                                          \
-        (void)adw_s; (void)adw_n; (void)adb_c; (void)adb_n;                                                            \
-        if ((T) == 1) g8_wait_vm<WPI + NIA>();                                                                         \
-        else if ((T) >= 7 && MFP == 2) { if (last) g8_wait_vm<1>(); else g8_wait_vm<2>(); }                            \
-        else g8_wait_vm<WPI>();                                                                                        \
-        __builtin_amdgcn_s_barrier();                                                                                  \
-        if constexpr (DY == 0) g8_wait_lgkm<0>(); else g8_wait_lgkm<1>();                                              \
-        __builtin_amdgcn_sched_barrier(0);
-#define G8_STEP_DMA(T, MFP)                                                                                            \
-        if ((T) == 6 && last) wptr = w_next;                                                                           \
-        if ((T) == 0) { if (use_nxt_off) issue_act(act_f, aoff_nxt, nxt); else issue_act(act_f, aoff_cur, nxt); }      \
-        if ((T) >= 6 && last) {                                                                                        \
-            if constexpr (MFP == 2) { issue_wB(wptr, sl2); wptr += WSTEP_B; }                                          \
-            else { issue_wA(wptr, sl2); wptr += WSTEP_A; }                                                             \
-        } else {                                                                                                       \
-            if constexpr (MFP == 2) { issue_wA(wptr, sl2); wptr += WSTEP_A; }                                          \
-            else { issue_wB(wptr, sl2); wptr += WSTEP_B; }                                                             \
-        }                                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);
-    // two passes.  LDS reads in issue order: X: Ahi[0] (, Ahi[1]); dy < 2: row NF + dy.  Y: Alo'[0] (, Alo'[1]), the dying rows
-#define G8_STEP2(T, MFP)                                                                                               \
-    {                                                                                                                  \
-        G8_STEP_HEAD(T, MFP)                                                                                           \
-        G8_MM(Alo, 0, Bhi, DY, 0) G8_RD(Ahi[0], 0, adw_s)                                                              \
-        if constexpr (MFP == 2) { G8_MM(Alo, 1, Bhi, DY, 0) G8_RD(Ahi[1], 512, adw_s) }                                \
-        G8_MM(Alo, 0, Bhi, 1 + DY, 1)                                                                                  \
-        if constexpr (DY < 2) G8_RD(Bhi[NF + DY], G8_ROW(NF + DY, DX, 0), adb_c)                                       \
-        if constexpr (MFP == 2) G8_MM(Alo, 1, Bhi, 1 + DY, 1)                                                          \
-        G8_MM(Alo, 0, Bhi, 2 + DY, 2)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Alo, 1, Bhi, 2 + DY, 2)                                                          \
-        G8_MM(Alo, 0, Bhi, 3 + DY, 3)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Alo, 1, Bhi, 3 + DY, 3)                                                          \
-        G8_STEP_DMA(T, MFP)                                                                                            \
-        g8_wait_lgkm<(DY < 2 ? 1 : 0)>();                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        G8_MM(Ahi, 0, Bhi, DY, 0) G8_RD(Alo[0], 2048, adw_n)                                                           \
-        if constexpr (MFP == 2) { G8_MM(Ahi, 1, Bhi, DY, 0) G8_RD(Alo[1], 2048 + 512, adw_n) }                         \
-        if constexpr (DY == 0) G8_RD(Bhi[0], G8_ROW(0, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 1) G8_RD(Bhi[1], G8_ROW(1, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 2) G8_RD(Bhi[2], G8_ROW(2, NDX, 0), adb_n)                                                 \
-        G8_MM(Ahi, 0, Bhi, 1 + DY, 1)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Bhi, 1 + DY, 1)                                                          \
-        if constexpr (DY == 2) G8_RD(Bhi[3], G8_ROW(3, NDX, 0), adb_n)                                                 \
-        G8_MM(Ahi, 0, Bhi, 2 + DY, 2)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Bhi, 2 + DY, 2)                                                          \
-        G8_MM(Ahi, 0, Bhi, 3 + DY, 3)                                                                                  \
-        if constexpr (MFP == 2) G8_MM(Ahi, 1, Bhi, 3 + DY, 3)                                                          \
-        sl = sl1;                                                                                                      \
-    }
-    // one pass: A fragments double-buffered (PA: this step's, PB: the next step's, fetched behind the barrier), row by row
-#define G8_STEP1(T, MFP, PA, PB)                                                                                       \
-    {                                                                                                                  \
-        G8_STEP_HEAD(T, MFP)                                                                                           \
-        G8_RD(PB[0], 0, adw_n)                                                                                         \
-        if constexpr (MFP == 2) G8_RD(PB[1], 512, adw_n)                                                               \
-        if constexpr (DY < 2) G8_RD(Bhi[NF + DY], G8_ROW(NF + DY, DX, 0), adb_c)                                       \
-        G8_MM(PA, 0, Bhi, DY, 0)                                                                                       \
-        if constexpr (MFP == 2) G8_MM(PA, 1, Bhi, DY, 0)                                                               \
-        if constexpr (DY == 0) G8_RD(Bhi[0], G8_ROW(0, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 1) G8_RD(Bhi[1], G8_ROW(1, NDX, 0), adb_n)                                                 \
-        if constexpr (DY == 2) G8_RD(Bhi[2], G8_ROW(2, NDX, 0), adb_n)                                                 \
-        G8_STEP_DMA(T, MFP)                                                                                            \
-        G8_MM(PA, 0, Bhi, 1 + DY, 1)                                                                                   \
-        if constexpr (MFP == 2) G8_MM(PA, 1, Bhi, 1 + DY, 1)                                                           \
-        if constexpr (DY == 2) G8_RD(Bhi[3], G8_ROW(3, NDX, 0), adb_n)                                                 \
-        G8_MM(PA, 0, Bhi, 2 + DY, 2)                                                                                   \
-        if constexpr (MFP == 2) G8_MM(PA, 1, Bhi, 2 + DY, 2)                                                           \
-        G8_MM(PA, 0, Bhi, 3 + DY, 3)                                                                                   \
-        if constexpr (MFP == 2) G8_MM(PA, 1, Bhi, 3 + DY, 3)                                                           \
-        sl = sl1;                                                                                                      \
-    }
-#define G8_CHUNK(MFP)                                                                                                  \
-    if constexpr (PASSES == 3) {                                                                                       \
-        G8_STEP(0, MFP) G8_STEP(1, MFP) G8_STEP(2, MFP) G8_STEP(3, MFP) G8_STEP(4, MFP) G8_STEP(5, MFP) G8_STEP(6, MFP) \
-        G8_STEP(7, MFP) G8_STEP(8, MFP)                                                                                \
-    } else {                                                                                                           \
-        G8_STEP2(0, MFP) G8_STEP2(1, MFP) G8_STEP2(2, MFP) G8_STEP2(3, MFP) G8_STEP2(4, MFP) G8_STEP2(5, MFP)          \
-        G8_STEP2(6, MFP) G8_STEP2(7, MFP) G8_STEP2(8, MFP)                                                             \
-    }
-#define G8_CHUNK1(MFP, PA, PB)                                                                                         \
-    G8_STEP1(0, MFP, PA, PB) G8_STEP1(1, MFP, PB, PA) G8_STEP1(2, MFP, PA, PB) G8_STEP1(3, MFP, PB, PA)                \
-    G8_STEP1(4, MFP, PA, PB) G8_STEP1(5, MFP, PB, PA) G8_STEP1(6, MFP, PA, PB) G8_STEP1(7, MFP, PB, PA)                \
-    G8_STEP1(8, MFP, PA, PB)
-
-    // ---- C8S stores: the lane's channel quads (r >> 2 = j) of a pair (2 jp, 2 jp + 1) are completed to 8-channel groups with
-    // lane ^ 32 (v_permlane32_swap), after which the lane holds group 2 jp + kg of the wave's 32-channel block
-    auto split_pair = [&](const float (&va)[4], const float (&vb)[4], u32x4 &hi, u32x4 &lo) {
-        unsigned ha[2], la[2], hb[2], lb[2];
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            const float x0 = va[2 * d] * a.act_scale, x1 = va[2 * d + 1] * a.act_scale;
-            const float y0 = vb[2 * d] * a.act_scale, y1 = vb[2 * d + 1] * a.act_scale;
-            const _Float16 a0 = (_Float16)x0, a1 = (_Float16)x1, b0 = (_Float16)y0, b1 = (_Float16)y1;
-            ha[d] = g8_pack_h2(a0, a1);
-            la[d] = g8_pack_h2((_Float16)(x0 - (float)a0), (_Float16)(x1 - (float)a1));
-            hb[d] = g8_pack_h2(b0, b1);
-            lb[d] = g8_pack_h2((_Float16)(y0 - (float)b0), (_Float16)(y1 - (float)b1));
         }
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-            auto r = __builtin_amdgcn_permlane32_swap(ha[d], hb[d], false, false);
-            ha[d] = r[0]; hb[d] = r[1];
-            auto q = __builtin_amdgcn_permlane32_swap(la[d], lb[d], false, false);
-            la[d] = q[0]; lb[d] = q[1];
-        }
-        hi = (u32x4){ha[0], ha[1], hb[0], hb[1]};
-        lo = (u32x4){la[0], la[1], lb[0], lb[1]};
-    };
 
+    auto split_pair = [&](const float (&va)[4], const float (&vb)[4], u32x4 &hi, u32x4 &lo) { c8_split_pair(va, vb, a.act_scale, hi, lo); };
     unsigned target = 0, target_raw = 0;       // the flag value this launch publishes for its tiles
     auto read_target = [&]() {                 // (the load is waited for at the gate, not here)
         target_raw = __hip_atomic_load((g8_gu32 *)a.flags + tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -478,8 +241,8 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
             float v[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                acc[0][n][r] = g8_sigmoid(__fmul_rn(acc[0][n][r], a.s_zr));
-                v[r] = __fmul_rn(g8_sigmoid(__fmul_rn(acc[1][n][r], a.s_zr)), hv[n & 1][r]);
+                acc[0][n][r] = c8_sigmoid(__fmul_rn(acc[0][n][r], a.s_zr));
+                v[r] = __fmul_rn(c8_sigmoid(__fmul_rn(acc[1][n][r], a.s_zr)), hv[n & 1][r]);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -533,7 +296,7 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float z = acc[0][n][r];
-                const float q = g8_tanh(__fmul_rn(acc[1][n][r], a.s_q));
+                const float q = c8_tanh(__fmul_rn(acc[1][n][r], a.s_q));
                 v[r] = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, z), hv[n & 1][r]), __fmul_rn(z, q));
             }
             if (inside) {
@@ -591,11 +354,11 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
         wptr += WSTEP_A;
     }
     init_A(b, h0, w0);
-    g8_wait_vm<0>();
+    c8_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     int g = 0;              // chunks consumed by this block: activation buffer parity
     int sl = 0;             // ring slot of the step being computed
-    G8_FIRST_FRAGS(2)
+    C8_FIRST_FRAGS(2, g)
     // @trace(1)
     for (;;) {
         const int tn = tile + blk_count;
@@ -612,18 +375,18 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
             const int cur = g & 1, nxt = cur ^ 1;
         if constexpr (PASSES == 1) {
             for (int c = 0; c < nA; c += 2) {
-                { G8_A_SETUP(c) G8_CHUNK1(2, Ahi, Alo) }
+                { G8_A_SETUP(c) C8_CHUNK1(2, Ahi, Alo) }
                 ++g;
-                { G8_A_SETUP(c + 1) G8_CHUNK1(2, Alo, Ahi) }
+                { G8_A_SETUP(c + 1) C8_CHUNK1(2, Alo, Ahi) }
                 ++g;
             }
         } else {
             for (int c = 0; c < nA; ++c, ++g) {
                 G8_A_SETUP(c)
-                G8_CHUNK(2)
+                C8_CHUNK(2)
             }
         }
-        g8_wait_lgkm<0>();
+        c8_wait_lgkm<0>();
         // @trace(2)
         target = __builtin_amdgcn_readfirstlane(target_raw + 1u);
         gate_A();
@@ -631,7 +394,7 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (tid == 0) __hip_atomic_store((g8_gu32 *)a.flags + tile, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        G8_FIRST_FRAGS(1)
+        C8_FIRST_FRAGS(1, g)
         // @trace(3)
         // ---------------- phase B: q
 #define G8_B_SETUP(c)                                                                                                  \
@@ -644,18 +407,18 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
             const int cur = g & 1, nxt = cur ^ 1;
         if constexpr (PASSES == 1) {
             for (int c = 0; c < nB; c += 2) {
-                { G8_B_SETUP(c) G8_CHUNK1(1, Ahi, Alo) }
+                { G8_B_SETUP(c) C8_CHUNK1(1, Ahi, Alo) }
                 ++g;
-                { G8_B_SETUP(c + 1) G8_CHUNK1(1, Alo, Ahi) }
+                { G8_B_SETUP(c + 1) C8_CHUNK1(1, Alo, Ahi) }
                 ++g;
             }
         } else {
             for (int c = 0; c < nB; ++c, ++g) {
                 G8_B_SETUP(c)
-                G8_CHUNK(1)
+                C8_CHUNK(1)
             }
         }
-        g8_wait_lgkm<0>();
+        c8_wait_lgkm<0>();
         // @trace(4)
         gate_B();
         // @trace(5)
@@ -665,9 +428,9 @@ __global__ __launch_bounds__(512, 1) void gru_c8_kernel(G8ArgsPair ap, int nb0) 
         for (int j = 0; j < NIA; ++j) aoff_cur[j] = aoff_nxt[j];
         read_target();
         init_A(b, h0, w0);
-        G8_FIRST_FRAGS(2)
+        C8_FIRST_FRAGS(2, g)
     }
-    g8_wait_vm<0>();        // no DMA may land in this block's LDS after it has been released
+    c8_wait_vm<0>();        // no DMA may land in this block's LDS after it has been released
 }
 
 // ---------------------------------------------------------------------------------------------------------

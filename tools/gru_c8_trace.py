@@ -1,7 +1,8 @@
 """Phase timeline of the fused ConvGRU kernel: builds a tools-side copy of csrc/gru_c8.hip whose `// @trace(k)` markers
 store s_memrealtime (100 MHz) per block behind the error word, runs the cfg2 gru08 (+ gru32) launch and prints the
 per-phase durations (median / min / max over blocks).  Optional text substitutions make timing-only variants
-(`--sub 'gate_A();=>'`): the product source carries no ablation branches."""
+(`--sub 'gate_A();=>'`): the product source carries no ablation branches.  Substitutions also reach the (chunk, tap) step: they
+are applied to a copy of csrc/c8_pipe.h as well (tools/c8_variant.py)."""
 import ctypes
 import os
 import subprocess
@@ -12,6 +13,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
 OUT = os.path.join(HERE, "_build")
 
 
@@ -20,7 +22,8 @@ TAG = ([a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--tag=")] or [
 
 def build(subs, trace=True):
     from dkt_stereo_amd import build as B
-    os.makedirs(OUT, exist_ok=True)
+    from c8_variant import write_variant
+    B.build()
     src = open(os.path.join(B.CSRC, "gru_c8.hip")).read()
     if trace:
         import re
@@ -34,18 +37,12 @@ def build(subs, trace=True):
         a = "        tile = tn; b = nb; txy = ntxy; h0 = nh0; w0 = nw0;\n"
         assert a in src
         src = src.replace(a, a + "        ++trace_round;\n        if (tid == 0) ((unsigned long long *)(ap.err + 16))[(trace_round * gridDim.x + blockIdx.x) * 8 + 0] = __builtin_amdgcn_s_memrealtime();\n", 1)
-        a = "        init_A(b, h0, w0);\n        G8_FIRST_FRAGS(2)\n    }\n"
+        a = "        init_A(b, h0, w0);\n        C8_FIRST_FRAGS(2, g)\n    }\n"
         assert a in src
-        src = src.replace(a, "        init_A(b, h0, w0);\n        G8_FIRST_FRAGS(2)\n        if (tid == 0) ((unsigned long long *)(ap.err + 16))[(trace_round * gridDim.x + blockIdx.x) * 8 + 1] = __builtin_amdgcn_s_memrealtime();\n    }\n", 1)
-    for sub in subs:
-        a, b = sub.split("=>")
-        assert a in src, a
-        src = src.replace(a, b)
-    src = src.replace('#include "dkt_common.h"', '#include "%s/dkt_common.h"' % B.CSRC)
-    path = os.path.join(OUT, "gru_c8_trace%s.hip" % TAG)
-    open(path, "w").write(src)
+        src = src.replace(a, "        init_A(b, h0, w0);\n        C8_FIRST_FRAGS(2, g)\n        if (tid == 0) ((unsigned long long *)(ap.err + 16))[(trace_round * gridDim.x + blockIdx.x) * 8 + 1] = __builtin_amdgcn_s_memrealtime();\n    }\n", 1)
+    path = write_variant(B, src, [sub.split("=>") for sub in subs], "gru_c8_trace%s" % TAG)
     obj = os.path.join(OUT, "gru_c8_trace%s.o" % TAG)
-    subprocess.check_call([B.HIPCC] + B.CFLAGS + B.EXTRA_FLAGS["gru_c8"] + ["-c", path, "-o", obj])
+    subprocess.check_call([B.HIPCC] + B.CFLAGS + B.EXTRA_FLAGS["gru_c8"] + ["-I", B.CSRC, "-c", path, "-o", obj])
     objs = [os.path.join(B.OBJ_DIR, f) for f in sorted(os.listdir(B.OBJ_DIR)) if f.endswith(".o") and f != "gru_c8.o"]
     lib = os.path.join(OUT, "libdktstereo_trace%s.so" % TAG)
     subprocess.check_call([B.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", obj] + objs + ["-o", lib])
