@@ -212,6 +212,8 @@ SIGNATURES = {
     "dkt_conv2d_dgrad_s2": [_vp, _l, _vp, _vp, _f, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_conv2d_wgrad_s2_ws_floats": [_i, _i, _i, _i, _i, _i],
     "dkt_conv2d_wgrad_s2": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "dkt_conv2d_wgrad7_ws_floats": [_i, _i, _i, _i, _i],
+    "dkt_conv2d_wgrad7": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_conv2d_f16s_dscale": [_pp, _ip, _lp, _i, _vp, _vp, _f, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_instance_norm_stats": [_vp, _vp, _i, _l, _i, _vp],
     "dkt_instance_norm_add_relu": [_vp, _vp, _vp, _vp, _i, _l, _f, _i, _vp],
@@ -242,7 +244,7 @@ SIGNATURES = {
     "dkt_interp_bilinear_bwd": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }
 #: entry points that do not return an int status
-RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long}
+RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long}
 
 #: DKT_E_UNSUPPORTED of include/dktstereo.h
 E_UNSUPPORTED = -7

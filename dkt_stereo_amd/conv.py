@@ -660,7 +660,8 @@ def conv2d_gate_out(x, q_layer, cq, z, h, out=None):
 # the input gradient run on this library's convolution kernels (the input gradient of a stride-1 same convolution is the
 # same convolution with the weights transposed over (Cout, Cin) and rotated by 180 degrees), the weight gradient -- a
 # reduction over all pixels, a different loop nest -- on dkt_conv2d_wgrad for 1x1 and 3x3 layers (GRAD_WEIGHT_HIP) and on the
-# vendor library (torch.nn.grad.conv2d_weight) for 7x7 ones, the bias gradient is a sum.
+# vendor library (torch.nn.grad.conv2d_weight) for 7x7 ones (on dkt_conv2d_wgrad7 with GRAD_WEIGHT7_HIP, for the stem layers'
+# 1..4 input channels), the bias gradient is a sum.
 #
 # Backward with GRAD_PREPASS (default): one streaming pre-pass (dkt_conv_grad_prepass) masks the upstream gradient with the
 # saved ReLU output, sums the bias gradient in a fixed order and leaves the RANGE of the masked gradient in device memory;
@@ -786,8 +787,8 @@ def conv2d_dscale(g, layer, scale, pack_scale=None):
 
 
 #: weight gradient of conv2d_autograd's 1x1 and 3x3 layers: True = dkt_conv2d_wgrad (csrc/conv_wgrad.hip), False = the vendor
-#: library (torch.nn.grad.conv2d_weight) fed with the same g' -- an A/B handle like GRAD_PREPASS; 7x7 layers, GRAD_PREPASS =
-#: False, CPU tensors and other dtypes stay on the vendor call either way
+#: library (torch.nn.grad.conv2d_weight) fed with the same g' -- an A/B handle like GRAD_PREPASS; 7x7 layers (but for
+#: GRAD_WEIGHT7_HIP below), GRAD_PREPASS = False, CPU tensors and other dtypes stay on the vendor call either way
 GRAD_WEIGHT_HIP = True
 #: (Cin, Cout, K) classes that stay on the vendor call with the handle on: rows of `tools/bench_gru_train.py --wgrad` that lost
 #: to it at B = 2 (us of dkt_conv2d_wgrad vs us of the vendor call)
@@ -830,6 +831,37 @@ def conv2d_wgrad(x, g, scale, k, x_scale=1.0, stride=1):
 def conv2d_wgrad_s2(x, g, scale, k, x_scale=1.0):
     """conv2d_wgrad at stride 2."""
     return conv2d_wgrad(x, g, scale, k, x_scale, stride=2)
+
+
+#: weight gradient of conv2d_autograd's 7x7 stride-1 layers with at most WGRAD7_MAX_CIN input channels (the encoders' conv1,
+#: the motion encoders' convf1 / convd1): True = dkt_conv2d_wgrad7 (csrc/conv_wgrad7.hip), False = the vendor library fed with
+#: the same g'.  Needs GRAD_WEIGHT_HIP and the pre-pass; wider or stride-2 7x7 layers, CPU tensors and other dtypes stay on
+#: the vendor call either way.  Off: an A/B handle in the manner of extractor.TRAIN_CONV_NODES (DESIGN 3.18)
+GRAD_WEIGHT7_HIP = False
+WGRAD7_MAX_CIN = 4
+
+
+def conv2d_wgrad7(x, g, scale, x_scale=1.0):
+    """dkt_conv2d_wgrad7: the (Cout, Cin, 7, 7) weight gradient of a 7x7, stride-1, padding-3 convolution with Cin <= 4 from
+    its input `x` (B, Cin, H, W) and the masked gradient `g` (B, Cout, H, W), both fp32 with dense batch elements (`g` may be a
+    view with a longer batch stride); `scale` is the device pair {2^e, 2^-e} conv_grad_prepass left for `g`, `x_scale` the
+    host power of two of the layer's forward activations.  Nothing is read back on the host."""
+    _ffi.require_gpu(x, g, scale)
+    B, cin, H, W = x.shape
+    cout = g.shape[1]
+    if tuple(g.shape) != (B, cout, H, W):
+        raise ValueError("conv2d_wgrad7: g %s does not match x %s" % (tuple(g.shape), tuple(x.shape)))
+    x, g = _dense_per_batch(x), _dense_per_batch(g)
+    L = _ffi.lib()
+    n = int(L.dkt_conv2d_wgrad7_ws_floats(B, cin, cout, H, W))
+    if n < 0:
+        _ffi.check(n, "dkt_conv2d_wgrad7_ws_floats")
+    gw = torch.empty((cout, cin, 7, 7), device=x.device, dtype=torch.float32)
+    ws = torch.empty(n, device=x.device, dtype=torch.float32)
+    rc = L.dkt_conv2d_wgrad7(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(), float(x_scale),
+                             gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, _ffi.device_of(x), _ffi.stream_of(x))
+    _ffi.check(rc, "dkt_conv2d_wgrad7")
+    return gw
 
 
 #: stride-2 (Cin, Cout, K) classes whose weight gradient stays on the vendor call with the handle on: rows of
@@ -907,8 +939,10 @@ class _Conv2dGradFn(torch.autograd.Function):
                 vendor_classes = WGRAD_VENDOR_CLASSES
             wgrad = (need_w and GRAD_WEIGHT_HIP and kh == kw and kh in (1, 3) and x.is_cuda and gy.is_cuda
                      and x.dtype == torch.float32 and cls not in vendor_classes)
+            wgrad7 = (need_w and GRAD_WEIGHT7_HIP and GRAD_WEIGHT_HIP and kh == kw == 7 and ctx.stride == 1
+                      and x.shape[1] <= WGRAD7_MAX_CIN and x.is_cuda and gy.is_cuda and x.dtype == torch.float32)
             g, scale = gy, None
-            if ctx.relu or need_b or dscale or wgrad:
+            if ctx.relu or need_b or dscale or wgrad or wgrad7:
                 g, gb, scale = conv_grad_prepass(gy, y if ctx.relu else None, want_bias=need_b)
             if need_x and ctx.stride == 2:
                 gx = (conv2d_dgrad_s2(g, shim, scale, x.shape[2:], shim.pack_scale) if dscale else
@@ -917,6 +951,8 @@ class _Conv2dGradFn(torch.autograd.Function):
                 gx = conv2d_dscale(g, shim, scale, shim.pack_scale) if dscale else conv2d(g, shim)
             if wgrad:
                 gw = conv2d_wgrad(x.detach(), g, scale, kh, 2.0 ** in_exp_of(ctx.owner), ctx.stride)
+            elif wgrad7:
+                gw = conv2d_wgrad7(x.detach(), g, scale, 2.0 ** in_exp_of(ctx.owner))
             elif need_w:
                 gw = torch.nn.grad.conv2d_weight(x.detach(), w.shape, g, stride=ctx.stride, padding=(kh // 2, kw // 2))
         gws = [None] * n if gw is None else list(gw.split(ctx.splits, 0)) if n > 1 else [gw]

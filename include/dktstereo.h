@@ -443,6 +443,25 @@ int dkt_conv2d_wgrad_s2(const float *x, long x_bstride, const float *g, long g_b
                         float *gw /* (Cout,Cin,K,K) dense */, float *ws,
                         int B, int Cin, int Cout, int H, int W, int K, int device, void *stream);
 
+/* ---- weight gradient of the 7x7 stem layers (training; core/extractor.py:140, :217 conv1 3 -> 64, core/update.py:73
+ * convf1 2 -> 64, meta_arch/igev_stereo/update.py:80 convd1 1 -> 64, under training) ----
+ * torch autograd's weight gradient through conv2d(x, w, b, padding=3) of a 7x7 stride-1 layer with 1 <= Cin <= 4:
+ *   gw[co][ci][ky][kx] = sum_{b,y,x} g[b,co,y,x] * x[b,ci,y+ky-3,x+kx-3],   any Cout, B, H, W >= 1.
+ * Operands, scale, x_scale and ws as dkt_conv2d_wgrad, and its contract in every point: both operands split into fp16
+ * hi + lo while staged, three v_mfma_f32_32x32x16_f16 products with fp32 accumulation, the GEMM columns are the (ci, ky, kx)
+ * triples; split-K over (batch element, band of rows) into ws, the same finishing kernel adds a weight's slices in ascending
+ * order and un-scales by scale[1] / x_scale.  No float atomics; the same bits from run to run, for every grid size and for
+ * the 16-byte and the 4-byte load path; a power-of-two multiple of g gives that multiple of gw bit for bit; a non-finite
+ * g or x comes out non-finite; the host reads nothing back.
+ *   ws: dkt_conv2d_wgrad7_ws_floats(B, Cin, Cout, H, W) floats (the negative code for a bad shape).
+ * Errors, before any device is touched: x, g, scale, gw or ws null DKT_E_NULL; a size <= 0, Cin > 4, a batch stride shorter
+ * than C*H*W, or x_scale not a positive finite power of two DKT_E_SHAPE. */
+long dkt_conv2d_wgrad7_ws_floats(int B, int Cin, int Cout, int H, int W);
+int dkt_conv2d_wgrad7(const float *x, long x_bstride, const float *g, long g_bstride,
+                      const float *scale /* device {s, 1/s} of g */, float x_scale,
+                      float *gw /* (Cout,Cin,7,7) dense */, float *ws,
+                      int B, int Cin, int Cout, int H, int W, int device, void *stream);
+
 /* dkt_conv2d_f16s (stride 1, no bias, no ReLU, no epilogue) with the activation scale in DEVICE memory: the input-gradient
  * convolution, whose operand range only the device knows.  scale = {s, 1/s} as dkt_conv_grad_prepass writes it:
  *   in_scale = scale[0],  out_scale = w_inv_scale * scale[1]   (w_inv_scale: 1 / the weight scale of the pack),
