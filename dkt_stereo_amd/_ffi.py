@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("DKT_LIB_PATH") or os.path.join(_HERE, "lib", "libdkts
 
 _c_f32p = ctypes.c_void_p
 _i, _l, _f, _vp = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
+_d = ctypes.c_double
 _pp = ctypes.POINTER(ctypes.c_void_p)
 _ip = ctypes.POINTER(ctypes.c_int)
 _lp = ctypes.POINTER(ctypes.c_long)
@@ -238,13 +239,15 @@ SIGNATURES = {
     "dkt_instance_norm": [_vp, _vp, _vp, _i, _l, _f, _i, _i, _vp],
     "dkt_add_relu": [_vp, _vp, _vp, _l, _i, _vp],
     "dkt_ema_update": [_vp, _vp, _vp, _i, _f, _f, _vp, _i, _vp],
+    "dkt_adamw_workspace": [_i, _l],
+    "dkt_adamw_step": [_vp, _vp, _vp, _vp, _vp, _i, _l, _d, _d, _d, _d, _d, _d, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "dkt_pool2x": [_vp, _vp, _l, _i, _i, _i, _vp],
     "dkt_interp_bilinear": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
     "dkt_pool2x_bwd": [_vp, _vp, _l, _i, _i, _i, _vp],
     "dkt_interp_bilinear_bwd": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }
 #: entry points that do not return an int status
-RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long}
+RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long, "dkt_adamw_workspace": ctypes.c_long}
 
 #: DKT_E_UNSUPPORTED of include/dktstereo.h
 E_UNSUPPORTED = -7

@@ -713,6 +713,22 @@ class _Conv2dFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
+def _forward_pack_scale(owner, key):
+    """The scale of `owner`'s current forward image (None when its forward runs on a kernel without one)."""
+    scale = None
+    for lst in owner.__dict__.get("_dkt_packed", {}).values():
+        for p in lst:
+            if p.key.tensors[0] == key.tensors[0]:
+                scale = 1.0 / p.inv_scale
+    return scale
+
+
+def _grad_weight(w, out=None):
+    """`w` transposed over (Cout, Cin) and rotated by 180 degrees, fp32 and dense (into `out` when given)."""
+    wt = w.detach().float().transpose(0, 1).flip(2, 3)
+    return wt.contiguous() if out is None else out.copy_(wt)
+
+
 def _grad_layer(owner):
     """The layer of the input gradient -- `owner`'s weight transposed over (Cout, Cin) and rotated by 180 degrees -- as a
     persistent object on `owner`, per device, keyed on the weight's wcache.Key; its own packed image hangs off it
@@ -723,20 +739,32 @@ def _grad_layer(owner):
     with wcache.LOCK:
         hit = wcache.lookup(owner, "_dkt_grad", slot, key)
         if hit is not None:
+            hit.value.pack_scale = _forward_pack_scale(owner, key)
             return hit.value
         kh, kw = w.shape[2:]
         with torch.no_grad():
-            shim = _LayerShim(w.detach().float().transpose(0, 1).flip(2, 3).contiguous(), None, (kh // 2, kw // 2))
-        shim.pack_scale = None
-        for lst in owner.__dict__.get("_dkt_packed", {}).values():
-            for p in lst:
-                if p.key.tensors[0] == key.tensors[0]:
-                    shim.pack_scale = 1.0 / p.inv_scale
+            shim = _LayerShim(_grad_weight(w), None, (kh // 2, kw // 2))
+        shim.pack_scale = _forward_pack_scale(owner, key)
         wcache.store(owner, "_dkt_grad", slot, wcache.Entry(key, shim))
         return shim
 
 
-wcache.register("_dkt_grad", weights=False)
+def _refresh_grad(owner, cache, R):
+    """ema.refresh_written: the input-gradient layers of `owner` rewritten in place from its updated weight.  Returns them:
+    their own packed images are refreshed next, at their existing scales, so the next backward packs nothing."""
+    out = []
+    for e, _ in R.each(cache):
+        shim = e.value
+        R.write(shim.weight, lambda: _grad_weight(owner.weight, shim.weight))
+        hit = R.index.get(owner.weight.data_ptr())
+        if hit is not None and owner.weight.dtype == torch.float32:          # (the same elements: the same max|w|)
+            R.index[shim.weight.data_ptr()] = hit
+        e.key = R.rekey(e.key)
+        out.append(shim)
+    return out
+
+
+wcache.register("_dkt_grad", _refresh_grad, derived=True)
 
 
 def _dscale_eligible(shim):

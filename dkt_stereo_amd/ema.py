@@ -37,7 +37,7 @@ class _Refresh:
     def __init__(self):
         self.vmap = {}            # data_ptr -> (version before, version after)
         self.gone = set()         # data_ptrs of parameters the fallback replaced
-        self.flags, self.drops = [], []
+        self.amaxes, self.invs, self.drops = [], [], []   # per repacked image: max|w| (device), its 1 / scale, its drop()
         self.unknown = []         # caches no hook refreshed
         self.absmax = None
         self.index = {}           # data_ptr -> (position in absmax, numel) of the kernel's parameters
@@ -89,10 +89,26 @@ class _Refresh:
         return w.detach().float().abs().amax()
 
     def window(self, amax, inv_scale, drop):
-        s = amax / inv_scale
-        self.flags.append((s >= 2.0 ** WINDOW_LO) & (s < 2.0 ** WINDOW_HI))
+        if torch.is_tensor(inv_scale):         # (a pack's scale is a host number; float() of a device tensor would be a host read)
+            raise TypeError("_Refresh.window: inv_scale is a Python number")
+        self.amaxes.append(amax)
+        self.invs.append(float(inv_scale))
         self.drops.append(drop)
         self.repacked += 1
+
+    def flags(self):
+        """Whether each repacked image's max|w| * scale lies in the window: one bool tensor per device, in a handful of
+        launches for all images (the scales travel through pinned memory, without blocking), with the positions it covers."""
+        by_dev = {}
+        for i, a in enumerate(self.amaxes):
+            by_dev.setdefault(a.device, []).append(i)
+        out = []
+        for dev, idx in by_dev.items():
+            inv = torch.tensor([self.invs[i] for i in idx], dtype=torch.float32)
+            inv = inv.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else inv
+            s = torch.stack([self.amaxes[i].reshape(()).float() for i in idx]) / inv
+            out.append((idx, (s >= 2.0 ** WINDOW_LO) & (s < 2.0 ** WINDOW_HI)))
+        return out
 
 
 _TABLES = {}
@@ -136,11 +152,12 @@ def _unwrap(m):
     return m.module if isinstance(m, (nn.DataParallel, nn.parallel.DistributedDataParallel)) else m
 
 
-def _refresh(teacher, R):
+def _refresh(teacher, R, extra=()):
     """Rewrites every current weight derivative below `teacher` in place; returns True when the captured states may be
     re-keyed (nothing unknown, every scale window held -- read with the call's one host synchronisation).  Derived layers
     carry caches of their own (a folded layer's merged heads, a layer view's head weights, every pack): they are visited
-    after the layers they derive from, breadth first."""
+    after the layers they derive from, breadth first.  `extra`: 0-d bool device tensors of the caller, read in the same
+    host read and left in R.extra."""
     todo, seen, holders = list(teacher.modules()), set(), []
     while todo:
         h = todo.pop(0)
@@ -162,12 +179,39 @@ def _refresh(teacher, R):
             if cache:
                 hook(h, cache, R)
     ok = not R.unknown
-    if R.flags:
-        bits = torch.stack(R.flags).cpu().tolist()          # the one host read of the call
-        for good, drop in zip(bits, R.drops):
+    R.extra = []
+    if R.amaxes or extra:
+        groups = R.flags()
+        parts = [f for _, f in groups] + ([torch.stack(list(extra))] if extra else [])
+        if len({t.device for t in parts}) > 1:             # (parameters across devices: one read per device)
+            parts = [t.cpu() for t in parts]
+        flat = torch.cat(parts).cpu()                      # the one host read of the call
+        bits = flat.tolist()
+        order = [i for idx, _ in groups for i in idx]
+        R.extra = bits[len(order):]
+        for i, good in zip(order, bits):
             if not good:
-                drop()
+                R.drops[i]()
                 ok = False
+    return ok
+
+
+def refresh_written(module, tensors, R, extra=()):
+    """After a kernel has written the parameters `tensors` of `module` in place (R.absmax / R.index: its max|w| per tensor):
+    bumps their version counters once, rewrites every weight derivative that was current before the write into its existing
+    buffers at its existing scale and, when nothing was unknown and every scale window held, re-keys the captured states.
+    One host read (see _refresh).  Returns whether everything stayed warm.  ema_update_ and optim.AdamW.step() share it."""
+    olds = [t._version for t in tensors]
+    if tensors:
+        torch.autograd.graph.increment_version(tensors)
+    for t, old in zip(tensors, olds):
+        R.vmap[t.data_ptr()] = (old, t._version)
+    ok = _refresh(module, R, extra) if tensors else False
+    if ok:
+        for m in module.modules():
+            rekey = getattr(m, "_ema_rekey", None)
+            if rekey is not None:
+                rekey(R)
     return ok
 
 
@@ -201,18 +245,9 @@ def ema_update_(teacher, student, decay):
             if len(by_dev) == 1:                           # (amax by reduction when the parameters span devices)
                 R.absmax = absmax
                 R.index = {t.data_ptr(): (i, t.numel()) for i, t in enumerate(ts)}
-        olds = [t._version for t in kernel]
-        if kernel:
-            torch.autograd.graph.increment_version(kernel)
-        for t, old in zip(kernel, olds):
-            R.vmap[t.data_ptr()] = (old, t._version)
+        for t in kernel:
             t.requires_grad = False
-        ok = _refresh(tm, R) if kernel else False
-        if ok:
-            for m in tm.modules():
-                rekey = getattr(m, "_ema_rekey", None)
-                if rekey is not None:
-                    rekey(R)
+        ok = refresh_written(tm, kernel, R)
     return dict(kernel=len(kernel), fallback=len(fallback), repacked=R.repacked, warm=ok,
                 unknown=[name for _, name in R.unknown])
 

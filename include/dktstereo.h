@@ -652,6 +652,31 @@ int dkt_add_relu(const float *a, const float *b, float *y, long n, int device, v
 int dkt_ema_update(float *const *t, const float *const *s, const long *n, int count, float decay, float one_minus_decay,
                    float *absmax, int device, void *stream);
 
+/* ---- AdamW step with gradient clipping and loss-scale handling (csrc/optim.hip) --------------------------------
+ * Replaces tools/ft_dkt.py:243-246 for the optimizer of :58 (AdamW, eps 1e-8),
+ *     scaler.unscale_(optimizer); torch.nn.utils.clip_grad_norm_(model.parameters(), 1.0); scaler.step(optimizer)
+ * for `count` tensors in at most three launches and without a host read.  p, g, exp_avg, exp_avg_sq: DEVICE tables of
+ * `count` tensor pointers (fp32, dense); n: DEVICE table of count + 1 exclusive prefix offsets as in dkt_ema_update;
+ * total = n[count], the host's copy (it sizes the grid and the workspace).  lr, beta1, beta2, eps, weight_decay by value on
+ * every call; max_norm < 0 = no clipping, +inf = take and report the norm without clipping (clip_grad_norm_'s own reading).  inv_scale (host) and *grad_scale (device, may be null) give the factor
+ * inv = inv_scale / *grad_scale applied to every gradient; *found_inf (device, may be null) != 0 skips the step, and so does
+ * any inf or nan in g.  step: DEVICE fp32 scalar, the number of steps taken, incremented unless the step is skipped.
+ * record: 4 DEVICE floats {total_norm (of g * inv), clip = min(1, max_norm / (total_norm + 1e-6)), skipped (0 / 1), inv}.
+ * A skipped step writes no parameter and no moment.  g is never written.  absmax (may be null): `count` floats, max |p_new|
+ * per tensor (of the unchanged p on a skipped step; 0 for an empty tensor).  workspace: dkt_adamw_workspace(count, total)
+ * bytes of device memory, 8-byte aligned, ZEROED before its first use; every call leaves it ready for the next.  grid: 0, or
+ * a block count that overrides the library's (tests: the results do not depend on it).  With max_norm < 0, inv_scale == 1
+ * and grad_scale == found_inf == null the call is ONE launch and record is {-1, 1, 0, 1}.  The rounding sequence is in
+ * csrc/optim.hip; every output is bit-identical from run to run.  count = 0 is a no-op.
+ * Errors, before any device is touched: count, total or grid < 0 DKT_E_SHAPE; a non-finite lr, beta, eps, weight_decay
+ * or inv_scale, a nan max_norm, a beta outside [0, 1), a negative lr, eps or weight_decay DKT_E_UNSUPPORTED; a table, step, record
+ * or workspace null DKT_E_NULL.  dkt_adamw_workspace: 64 + 8 * ceil(total / 2048), or -1 for a negative argument. */
+long dkt_adamw_workspace(int count, long total);
+int dkt_adamw_step(float *const *p, const float *const *g, float *const *exp_avg, float *const *exp_avg_sq, const long *n,
+                   int count, long total, double lr, double beta1, double beta2, double eps, double weight_decay,
+                   double max_norm, float inv_scale, const float *grad_scale, const float *found_inf, float *step,
+                   float *record, float *absmax, void *workspace, int grid, int device, void *stream);
+
 /* ---- round 3: the 3x3 convolution on pre-split activations ("C8S" layout, conv_c8.hip) -------------------------
  * Same operator and arithmetic as dkt_conv2d_f16s(passes = 3) -- core/update.py:19-21,27-31 (ConvGRU), :72-76,84
  * (motion encoder), :9 (FlowHead.conv1) -- but the activation operands arrive as fp16 (hi, lo) pairs written by the
