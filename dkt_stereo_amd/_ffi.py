@@ -174,6 +174,9 @@ SIGNATURES = {
     "dkt_context_upsample": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "dkt_convex_upsample_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_convex_upsample_bwd": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "dkt_context_upsample_bwd": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "dkt_context_upsample_logits_fwd": [_vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
+    "dkt_context_upsample_logits_bwd": [_vp, _l, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "dkt_corr1d_lookup_bwd": [_vp, _vp, _l, _pp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_geo_lookup_bwd": [_vp, _vp, _vp, _pp, _pp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_geo_pool_bwd": [_pp, _vp, _l, _i, _l, _i, _i, _vp],

@@ -24,6 +24,7 @@ from . import wcache
 from . import conv_c8 as c8
 from . import loop_c8
 from .conv import conv2d
+from .upsample import context_upsample_logits
 from .update import FUSE_GATES, GPU_GUARD, _side_stream, capture_graph, gru_pair, harness, interp, pool2x, replay_graph
 
 #: the coarsest GRU of the next iteration shares the finest GRU's two launches (dkt_conv2d_f16s_pair)
@@ -47,6 +48,36 @@ def _plain(update_block, geo_fn, disp, coords, net_list, inp_list, iters):
                                              need_mask=(itr == iters - 1))
         disp = disp + delta
     return disp, mask, net_list
+
+
+def upsample_disp(disp, mask_feat_4, stem_2x, spx_2_gru, spx_gru):
+    """IGEVStereo.upsample_disp (igev_stereo.py:140-148) with the caller's two modules: the softmax, the factor 4 and
+    context_upsample are one node (upsample.context_upsample_logits).  (B, 1, h, w) -> (B, 1, 4h, 4w)."""
+    return context_upsample_logits(disp, spx_gru(spx_2_gru(mask_feat_4, stem_2x)), 4.0).unsqueeze(1)
+
+
+def igev_iterate_train(update_block, geo_fn, init_disp, coords, net_list, inp_list, iters, upsample):
+    """igev_stereo.py:199-217 with test_mode=False: one up-sampled prediction per iteration,
+    ``upsample(disp, mask_feat_4)`` (e.g. upsample_disp with the model's stem features and modules bound), differentiable
+    when autograd is enabled -- the geometry lookup, the update block and the up-sampling are this library's autograd
+    nodes.  Returns (preds, disp, net_list); the reference's sign flip of the predictions (:216) stays with the caller.
+    No captured graph.  Under torch.no_grad() the same loop on the inference operators."""
+    n = update_block.args.n_gru_layers
+    slow_fast = getattr(update_block.args, "slow_fast_gru", False)
+    disp, net_list, preds = init_disp, list(net_list), []
+    with GPU_GUARD.shared():
+        for _ in range(iters):
+            disp = disp.detach()
+            geo_feat = geo_fn(disp, coords)
+            if n == 3 and slow_fast:
+                net_list = update_block(net_list, inp_list, iter16=True, iter08=False, iter04=False, update=False)
+            if n >= 2 and slow_fast:
+                net_list = update_block(net_list, inp_list, iter16=(n == 3), iter08=True, iter04=False, update=False)
+            net_list, mask_feat_4, delta = update_block(net_list, inp_list, geo_feat, disp, iter16=(n == 3), iter08=(n >= 2),
+                                                        need_mask=True)
+            disp = disp + delta
+            preds.append(upsample(disp, mask_feat_4))
+    return preds, disp, net_list
 
 
 class _State:

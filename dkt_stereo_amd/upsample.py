@@ -1,7 +1,10 @@
 """Convex up-sampling as an autograd node (RAFTStereo.upsample_flow on the training path, raft_stereo.py:70-82).
 
 Forward: dkt_convex_upsample_fwd, the leading `channels` channels, bit-identical to the inference kernel's.  Backward:
-dkt_convex_upsample_bwd, deterministic, the softmax recomputed from the mask (only flow and mask are saved)."""
+dkt_convex_upsample_bwd, deterministic, the softmax recomputed from the mask (only flow and mask are saved).
+
+IGEV's context up-sampling from logits (IGEVStereo.upsample_disp, igev_stereo.py:145-147) as one node:
+context_upsample_logits on dkt_context_upsample_logits_fwd / _bwd (context_upsample_train.hip)."""
 import torch
 
 from . import _ffi
@@ -61,3 +64,55 @@ def convex_upsample(flow, mask, factor, channels=None):
     if not 1 <= channels <= D:
         raise _ffi.DktError("channels = %d outside 1..%d" % (channels, D))
     return _ConvexUpsampleFn.apply(flow, mask, factor, channels)
+
+
+def _aligned16(t):
+    """`t` (contiguous) at a 16-byte aligned address: the nine-plane tensors are moved 16 bytes at a time."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+class _ContextUpsampleLogitsFn(torch.autograd.Function):
+    """The tail of IGEVStereo.upsample_disp (igev_stereo.py:145-147: softmax over the nine planes, disp * scale,
+    context_upsample) as one node: dkt_context_upsample_logits_fwd / _bwd, only disp and the logits saved."""
+
+    @staticmethod
+    def forward(ctx, disp_low, logits, scale):
+        B, _, h, w = disp_low.shape
+        out = torch.empty((B, 4 * h, 4 * w), device=disp_low.device, dtype=torch.float32)
+        rc = _ffi.lib().dkt_context_upsample_logits_fwd(disp_low.data_ptr(), logits.data_ptr(), scale, out.data_ptr(), B, h, w,
+                                                        _ffi.device_of(out), _ffi.stream_of(out))
+        _ffi.check(rc, "dkt_context_upsample_logits_fwd")
+        ctx.save_for_backward(disp_low, logits)
+        ctx.scale = scale
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        disp_low, logits = ctx.saved_tensors
+        need_disp, need_logits = ctx.needs_input_grad[:2]
+        if not (need_disp or need_logits):
+            return None, None, None
+        _ffi.require_gpu(gout)
+        B, _, h, w = disp_low.shape
+        g, bstride = _batch_strided(gout.float().unsqueeze(1))
+        gdisp = torch.empty_like(disp_low) if need_disp else None
+        glogits = torch.empty_like(logits) if need_logits else None
+        ws = torch.empty((B, 9, h, w), device=disp_low.device, dtype=torch.float32) if need_disp else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        rc = _ffi.lib().dkt_context_upsample_logits_bwd(g.data_ptr(), bstride, disp_low.data_ptr(), logits.data_ptr(), ctx.scale,
+                                                        ptr(gdisp), ptr(glogits), ptr(ws), B, h, w,
+                                                        _ffi.device_of(g), _ffi.stream_of(g))
+        _ffi.check(rc, "dkt_context_upsample_logits_bwd")
+        return gdisp, glogits, None
+
+
+def context_upsample_logits(disp_low, logits, scale=4.0):
+    """disp_low (B, 1, h, w), logits (B, 9, 4h, 4w) -> context_upsample(disp_low * scale, softmax(logits, 1)), (B, 4h, 4w),
+    in one pass and differentiable with respect to both.  `scale` is a positive power of two.  Tensors on a HIP device;
+    non-fp32 inputs are cast with .float()."""
+    disp_low, logits = disp_low.float(), logits.float()
+    _ffi.require_gpu(disp_low, logits)
+    B, c, h, w = disp_low.shape
+    if c != 1 or tuple(logits.shape) != (B, 9, 4 * h, 4 * w):
+        raise ValueError("context_upsample_logits: disp_low %s / logits %s" % (tuple(disp_low.shape), tuple(logits.shape)))
+    return _ContextUpsampleLogitsFn.apply(disp_low.contiguous(), _aligned16(logits.contiguous()), float(scale))

@@ -143,6 +143,41 @@ int dkt_convex_upsample_bwd(const float *gout, long gout_bstride, const float *f
                             float *gmask, float *ws, int N, int D, int Dout, int H, int W, int factor, int device,
                             void *stream);
 
+/* IGEV-Stereo's up-sampling on the training path (meta_arch/igev_stereo/igev_stereo.py:140-148, called once per refinement
+ * iteration at :215 and once for init_disp at :222 when test_mode=False).  disp_low (B,1,h,w); the nine-plane tensors
+ * (B,9,4h,4w); out / gout (B,4h,4w), gout with batch stride gout_bstride elements and its rows contiguous.  For fine pixel
+ * (Y,X) over coarse pixel (y,x) = (Y/4,X/4): nb_k = disp_low[b,0,y+k/3-1,x+k%3-1], 0 outside the image.
+ *
+ * Backward of context_upsample (torch autograd through meta_arch/igev_stereo/submodule.py:242-254; the forward is
+ * dkt_context_upsample):
+ *   gweights[b,k,Y,X] = gout[b,Y,X] * nb_k   (one rounding)
+ *   gdisp[b,0,y,x] = sum_k C[b,k,y-k/3+1,x-k%3+1] (terms outside the image absent),
+ *   C[b,k,y',x'] = sum_{i,j<4} up_weights[b,k,4y'+i,4x'+j] * gout[b,4y'+i,4x'+j].
+ * gdisp or gweights may be null (not wanted), not both.  ws: B*9*h*w floats of scratch, needed when gdisp is wanted.
+ * Deterministic (no atomics, one owner per element): the four products of a fine row are added in ascending j, the four
+ * row sums in ascending i, gdisp in ascending k.  One launch, plus one for gdisp.
+ * Errors (all three entries): a null pointer the call needs DKT_E_NULL; B, h, w <= 0 or a batch stride shorter than one
+ * image DKT_E_SHAPE; B > 65535 or h*w > 2^31 - 257 DKT_E_UNSUPPORTED; out / gout or a nine-plane tensor not aligned to 16
+ * bytes, or gout_bstride not a multiple of 4, DKT_E_ALIGN. */
+int dkt_context_upsample_bwd(const float *gout, long gout_bstride, const float *disp_low, const float *up_weights,
+                             float *gdisp, float *gweights, float *ws, int B, int h, int w, int device, void *stream);
+
+/* The tail of upsample_disp (igev_stereo.py:145-147: F.softmax(spx_pred, 1), disp*4., context_upsample) in one pass:
+ *   out[b,Y,X] = sum_k p_k v_k,  p_k = softmax_k(logits[b,:,Y,X]),  v_k = scale * nb_k,
+ * the softmax in the arithmetic of dkt_convex_upsample (max, expf(m - max), the sum in ascending k, one division each),
+ * out summed in ascending k with every product rounded.  scale: a finite positive power of two (v_k is then exact), else
+ * DKT_E_UNSUPPORTED. */
+int dkt_context_upsample_logits_fwd(const float *disp_low, const float *logits, float scale, float *out, int B, int h, int w,
+                                    int device, void *stream);
+
+/* Its backward (torch autograd through igev_stereo.py:145-147), the softmax recomputed from the logits:
+ *   a_k = gout * v_k,  s = sum_k p_k a_k,  glogits[b,k,Y,X] = p_k (a_k - s)
+ *   gdisp[b,0,y,x] = scale * sum_k C[b,k,y-k/3+1,x-k%3+1],  C = sum_{i,j<4} p_k * gout.
+ * Null gradients, ws, summation orders and errors as dkt_context_upsample_bwd. */
+int dkt_context_upsample_logits_bwd(const float *gout, long gout_bstride, const float *disp_low, const float *logits,
+                                    float scale, float *gdisp, float *glogits, float *ws, int B, int h, int w, int device,
+                                    void *stream);
+
 /* ---- backward of lookup / pyramid (autograd of core/corr.py:119-146) -------- */
 
 /* Gradient of every pyramid level from the gradient of one lookup's output:
