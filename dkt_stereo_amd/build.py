@@ -49,13 +49,20 @@ def build(force=False, verbose=False):
         return LIB
     os.makedirs(OBJ_DIR, exist_ok=True)
     # one object per source, compiled in parallel; conv2d.hip (the long pole: dozens of kernel
-    # instantiations) is compiled as seven translation units selected by -DCONV_TU_PASSES
+    # instantiations) is compiled as seven translation units selected by -DCONV_TU_PASSES, conv_c8.hip as four (-DC8_TU: the
+    # host side, and its kernel at one, two and three passes)
     jobs = []
     for src in sources():
         stem = os.path.splitext(os.path.basename(src))[0]
         if stem == "conv2d":
             for tu in (0, 1, 2, 3, 4, 5, 6):
                 jobs.append((src, os.path.join(OBJ_DIR, "conv2d_tu%d.o" % tu), ["-DCONV_TU_PASSES=%d" % tu]))
+        elif stem == "conv_c8":
+            old = os.path.join(OBJ_DIR, "conv_c8.o")       # (the single unit of earlier builds: the tools link every object here)
+            if os.path.exists(old):
+                os.remove(old)
+            for tu in (3, 2, 1, 0):
+                jobs.append((src, os.path.join(OBJ_DIR, "conv_c8_tu%d.o" % tu), EXTRA_FLAGS[stem] + ["-DC8_TU=%d" % tu]))
         else:
             jobs.append((src, os.path.join(OBJ_DIR, stem + ".o"), EXTRA_FLAGS.get(stem, [])))
 

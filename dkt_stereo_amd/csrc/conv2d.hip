@@ -394,6 +394,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
                 const int co = co_lane + m * 32 + (r & 3) + 8 * (r >> 2);
                 bv[m][r] = a.bias ? a.bias[co < a.Cout ? co : a.Cout - 1] : 0.0f;
             }
+        // The biases land HERE, once, and reach the stores below as values no load is pending on.  Left to the compiler, every
+        // use of a bias behind a guarded store got a drained wait of its own (it cannot count the stores a masked block issued):
+        // in the plain epilogue each of a row's 16 MF stores was waited on before the next one was issued.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int m = 0; m < MF; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bv[m][r]));
         const bool all_co = co_w + 32 * MF <= a.Cout;            // wave-uniform: no channel guard needed
         const int iHW = (int)HW;
         if (a.epi == 0) {

@@ -26,6 +26,13 @@
 
 #define C8_MAX_SRC 4
 
+// Translation units (build.py, as for conv2d.hip): the kernel's instantiations are the long pole of the build, so the file is
+// compiled once per value of C8_TU -- 0: the host side and the small kernels; 1, 2, 3: conv_c8_kernel at that many passes.
+// Without the definition the whole file is one unit (tools/c8_variant.py).
+#ifndef C8_TU
+#define C8_TU (-1)
+#endif
+
 struct C8Args {
     const char *src[C8_MAX_SRC];      // C8S tensors (all with the same Hp, Wp)
     long src_bs[C8_MAX_SRC];          // bytes per batch item
@@ -63,6 +70,36 @@ struct C8ArgsPair {
     C8Args p[2];
 };
 
+// A wave-uniform value pinned to scalar registers: what comes out cannot be recomputed (or re-loaded) from what went in.
+// (readfirstlane first: a uniform value the compiler computed on the vector ALU -- a division, say -- is in a vector register)
+__device__ __forceinline__ unsigned c8_hold(unsigned x) {
+    x = __builtin_amdgcn_readfirstlane(x);
+    asm volatile("" : "+s"(x));
+    return x;
+}
+__device__ __forceinline__ int c8_hold(int x) { return (int)c8_hold((unsigned)x); }
+__device__ __forceinline__ float c8_hold(float x) { return __uint_as_float(c8_hold(__float_as_uint(x))); }
+template <class T>
+__device__ __forceinline__ T *c8_hold(T *p) {
+    // (every pointer of the argument structure is a global one; rebuilt from two integers it would be a flat one)
+    const unsigned long long v = (unsigned long long)p;
+    return (T *)(__attribute__((address_space(1))) T *)(((unsigned long long)c8_hold((unsigned)(v >> 32)) << 32) | c8_hold((unsigned)v));
+}
+// The same for an address formed per access, without `volatile`: a volatile statement is a fence for the memory operations
+// around it (the loads of an operand batch would go out one by one); this one only cannot be folded into its neighbours.
+template <class T>
+__device__ __forceinline__ T *c8_base(T *p) {
+    unsigned long long v = (unsigned long long)p;
+    unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    asm("" : "+s"(lo), "+s"(hi));
+    return (T *)(__attribute__((address_space(1))) T *)(((unsigned long long)hi << 32) | lo);
+}
+template <int V>
+struct C8Tag {
+    static constexpr int value = V;
+};
+
+#if C8_TU != 0
 // WM x WN waves along (output channels, rows); wave tile 64 co x NF rows x 32 columns.
 // RING = weight ring slots: step s computes from slot s % RING while the images of steps s+1 .. s+RING-1 are in the ring or
 // on their way (short steps -- small wave tiles -- need the deeper rings to cover the DMA latency).
@@ -102,7 +139,6 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % WM, wn = wave / WM;
     const int li = lane & 31, kg = lane >> 5;
-    const long HW = (long)a.H * a.W;
 
     auto decode = [&](int t, int &th0, int &tw0, int &tco, int &tb) {
         const int xy = t % a.tiles_xy, r = t / a.tiles_xy;
@@ -195,42 +231,23 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
     // group instead of four strided 4-byte ones (a.f32_c4); NCHW remains for tensors other kernels read.
     // C8S outputs: c8_split_pair completes a pair of groups (j, j+1) to 8 consecutive channels per 16 bytes, after which the
     // lane stores group 2*jp + kg of its block.
-    auto store_c8_pair = [&](char *dst_b, int ch_block, int g_end, int jp, int oh, int ow, bool inside, const float (&va)[4], const float (&vb)[4]) {
-        u32x4 hi, lo;
-        c8_split_pair(va, vb, a.act_scale, hi, lo);
-        const int g = (ch_block >> 3) + 2 * jp + kg;
-        if (inside && g < g_end) {            // (groups past the destination's padded channel count do not exist)
-            char *p = dst_b + (long)g * 2 * a.out_c8_plane + ((long)(oh + 1) * a.out_c8_Wp + (ow + 1)) * 16;
-            *(u32x4 *)p = hi;
-            *(u32x4 *)(p + a.out_c8_plane) = lo;
-        }
-    };
-    // address of the 4 channels [c4, c4+4) of pixel px in an fp32 tensor (batch base already applied)
-    auto f32_ptr = [&](const float *base, int c4, long px, int iHW) -> const float * {
-        return a.f32_c4 ? base + ((long)(c4 >> 2) * iHW + px) * 4 : base + (long)c4 * iHW + px;
-    };
-    auto f32_load4 = [&](const float *p, int iHW, float (&v)[4]) {
-        if (a.f32_c4) {
-            const float4 t = *(const float4 *)p;
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = p[(long)i * iHW];
-        }
-    };
-    auto f32_store4 = [&](float *p, int iHW, const float (&v)[4], int nvalid) {
-        if (a.f32_c4) *(float4 *)p = make_float4(v[0], v[1], v[2], v[3]);      // (C4 tensors are padded to 4 channels)
-        else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nvalid) p[(long)i * iHW] = v[i];
-        }
-    };
+    // ARGUMENTS: `a` lives in the kernel-argument segment, so every `a.field` is a scalar load, and with the scalar registers
+    // this kernel has left the compiler re-issues that load (and waits for it) at each use instead of keeping the value.  At one
+    // wave per SIMD nothing hides those round trips, so the epilogues read what they need ONCE per tile into locals that
+    // c8_hold() makes opaque (a value that came out of an asm statement cannot be rematerialised as a load), decide the
+    // wave-uniform switches once (epilogue(): one dispatch to bodies specialised at compile time) and address every tensor as
+    // wave-uniform base + one 32-bit lane offset per row (the saddr + voffset form: no per-value 64-bit vector arithmetic).
     char *const lds_head = lds + 2 * ACT_BYTES + RING * WSLOT;      // epi 3 only: [wave][NF][9][32] floats
-    auto epilogue_head = [&]() {
-        const int co_w = co_blk + wm * 64;
-        const bool idle = co_w >= a.n_co64 * 64;
-        const int iHW = (int)HW;
+    auto epilogue_head = [&]() __attribute__((always_inline)) {
+        // (the arguments of this epilogue, read once per tile: see ARGUMENTS above)
+        const int H = c8_hold(a.H), W = c8_hold(a.W);
+        const int iHW = c8_hold(H * W);
+        const float out_scale = c8_hold(a.out_scale);
+        const float *const head_w = c8_hold(a.head_w);
+        const float *const bias_p = c8_hold(a.bias);
+        float *const head_out = c8_hold(a.head_out + (long)b * a.head_out_bs + (long)(co_blk / (64 * WM)) * 9 * iHW);
+        const int co_w = c8_hold(co_blk + wm * 64);
+        const bool idle = c8_hold((int)(co_w >= a.n_co64 * 64)) != 0;
         float *red = (float *)lds_head;
         int kgo = kg;                          // the lane's channel half, opaque from here on: nothing derived from it
         asm volatile("" : "+v"(kgo));          // can be pre-computed at kernel entry and kept live (spilled) through the main loop
@@ -251,15 +268,15 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         // channel co = cu + 4 kg: wave-uniform base pointers + one lane offset (Cout is a multiple of 64 here)
-                        const int cu = __builtin_amdgcn_readfirstlane(co_w) + m * 32 + (r & 3) + 8 * (r >> 2);
-                        const float *wp = a.head_w + (long)cu * 12 + kgo * 48;
+                        const int cu = co_w + m * 32 + (r & 3) + 8 * (r >> 2);
+                        const float *wp = head_w + (long)cu * 12 + kgo * 48;
                         const float4 w0 = *(const float4 *)wp, w1 = *(const float4 *)(wp + 4);
                         const float w8 = wp[8];
                         const float wt[9] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w8};
-                        const float bias = a.bias[cu + 4 * kgo];                 // (bias is mandatory here: a branch per channel wrecks the allocation)
+                        const float bias = bias_p[cu + 4 * kgo];                 // (bias is mandatory here: a branch per channel wrecks the allocation)
 #pragma unroll
                         for (int n = 0; n < NH; ++n) {
-                            const float v = dkt_relu(acc[m][n0 + n][r] * a.out_scale + bias);
+                            const float v = dkt_relu(acc[m][n0 + n][r] * out_scale + bias);
 #pragma unroll
                             for (int t = 0; t < 9; ++t) P[n][t] = __fmaf_rn(wt[t], v, P[n][t]);
                         }
@@ -288,115 +305,212 @@ __device__ __forceinline__ void conv_c8_body(const C8ArgsPair &ap, const int nb0
 #pragma unroll
                 for (int q = 1; q < WM; ++q) sum = __fadd_rn(sum, red[(((q + WM * wn) * NF + n) * 9 + t) * 32 + px]);
                 const int oh = h0 + wn * NF + n, ow = w0 + px;
-                if (oh < a.H && ow < a.W)
-                    a.head_out[(long)b * a.head_out_bs + ((long)(co_blk / (64 * WM)) * 9 + t) * iHW + (long)oh * a.W + ow] = sum;
+                if (oh < H && ow < W) head_out[(long)t * iHW + (long)oh * W + ow] = sum;
             }
         }
         __builtin_amdgcn_s_barrier();                            // `red` is free again before the next tile's epilogue
     };
-    auto epilogue = [&]() {
+    auto epilogue = [&]() __attribute__((always_inline)) {
+        const int epi = c8_hold(a.epi);
         if constexpr (NW == 8) {                 // (the two 8-wave shapes carry the head epilogue; round 4: in the NF = 4
-            if (a.epi == 3) {                    //  shapes its code costs hundreds of spilled registers)
+            if (epi == 3) {                      //  shapes its code costs hundreds of spilled registers)
                 epilogue_head();
                 return;
             }
         }
-        const int co_w = co_blk + wm * 64;
+        const int Cout = c8_hold(a.Cout);
+        const int co_w = c8_hold(co_blk + wm * 64);
         if (co_w >= a.n_co64 * 64) return;                   // idle wave
-        const int iHW = (int)HW;
-        const int Ch = a.epi == 1 ? a.Cout / 2 : a.Cout;
-        const bool rpart = a.epi == 1 && co_w >= Ch;         // wave-uniform: this wave owns r channels
-        const int cw = co_w - (rpart ? Ch : 0);              // first channel of this wave inside the Ch-wide tensors
+        // ---- per tile: every argument this epilogue needs, read once and held (see ARGUMENTS above)
+        const int H = c8_hold(a.H), W = c8_hold(a.W);
+        const int iHW = c8_hold(H * W);
+        const int Ch = epi == 1 ? Cout / 2 : Cout;           // channels of the destination tensors
+        const bool rpart = epi == 1 && co_w >= Ch;           // wave-uniform: this wave owns r channels
+        const int cw = c8_hold(co_w - (rpart ? Ch : 0));     // first channel of this wave inside the Ch-wide tensors
+        const float out_scale = c8_hold(a.out_scale), act_scale = c8_hold(a.act_scale);
+        const float *const bias_p = c8_hold(a.bias);
         // wave-uniform selections
-        const float *pc = a.epi ? (rpart ? a.e_c1 + (long)b * a.e_c1_bs : a.e_c0 + (long)b * a.e_c0_bs) : nullptr;
-        const float *pz = a.epi == 2 ? a.e_c1 + (long)b * a.e_c1_bs : nullptr;
-        const float *ph = (a.epi == 2 || rpart) ? a.e_h + (long)b * a.e_h_bs : nullptr;
-        float *po = rpart ? (a.out2 ? a.out2 + (long)b * a.out2_bs : nullptr) : (a.out ? a.out + (long)b * a.out_bs : nullptr);
-        char *pc8 = rpart ? (a.out2_c8 ? a.out2_c8 + (long)b * a.out2_c8_bs : nullptr) : (a.out_c8 ? a.out_c8 + (long)b * a.out_c8_bs : nullptr);
+        const float *const pc = c8_hold(epi ? (rpart ? a.e_c1 + (long)b * a.e_c1_bs : a.e_c0 + (long)b * a.e_c0_bs) : nullptr);
+        const float *const pz = c8_hold(epi == 2 ? a.e_c1 + (long)b * a.e_c1_bs : nullptr);
+        const float *const ph = c8_hold((epi == 2 || rpart) ? a.e_h + (long)b * a.e_h_bs : nullptr);
+        float *const po = c8_hold(rpart ? (a.out2 ? a.out2 + (long)b * a.out2_bs : nullptr) : (a.out ? a.out + (long)b * a.out_bs : nullptr));
+        char *const pc8 = c8_hold(rpart ? (a.out2_c8 ? a.out2_c8 + (long)b * a.out2_c8_bs : nullptr)
+                                        : (a.out_c8 ? a.out_c8 + (long)b * a.out_c8_bs : nullptr));
+        const int tail_ch = c8_hold(epi == 0 && a.tail ? a.tail_ch : 0);
+        const float *const ptail = c8_hold(tail_ch > 0 ? a.tail + (long)b * a.tail_bs : nullptr);
+        const float tail_ratio = c8_hold(a.tail_ratio);
         const int c8_ch0 = rpart ? a.out2_c8_ch0 : a.out_c8_ch0;
-        const int cout_eff = a.epi == 1 ? Ch : a.Cout;      // channels of the destination tensors
-        const int c8_gend = 2 * ((c8_ch0 + cout_eff + (a.epi == 0 ? a.tail_ch : 0) + 15) / 16);   // 8-channel groups the C8S destination holds
+        const int c8_g0 = c8_hold((c8_ch0 + cw) >> 3);                      // first 8-channel group of this wave in the C8S destination
+        const int c8_gend = c8_hold(2 * ((c8_ch0 + Ch + tail_ch + 15) / 16));   // 8-channel groups the C8S destination holds
+        const unsigned c8_plane = c8_hold((unsigned)a.out_c8_plane);        // (3 planes + a pixel fit 32 bits: the patch DMA offsets need that too)
+        const int c8_Wp = c8_hold(a.out_c8_Wp);
+        const int relu = c8_hold(a.relu), c4 = c8_hold(a.f32_c4);
+        // lane parts of the addresses: the lane's channel half (fp32: 4 kg channels = kg quads, 16 kg iHW bytes in both layouts)
+        // and column; a row adds wave-uniform terms
+        const unsigned kg_f32 = (unsigned)kg * 16u * (unsigned)iHW;
+        const unsigned kg_c8 = (unsigned)kg * 2u * c8_plane;
+        const int ow = w0 + li;
+        const bool col_in = ow < W;
+
+        // EPI: epilogue kind; C4: layout of the fp32 tensors; RPART (kind 1): the wave owns r channels.  ReLU is a select on a held
+        // flag; kinds 0 and 4 (the only ones whose channel count is free) test channels against the layer's last one per lane,
+        // and only their groups that can reach it (`rag`, wave-uniform) take the paths that differ: tail copy, clamped loads.
+        auto body = [&](auto kEpi, auto kC4, auto kRpart) __attribute__((always_inline)) {
+            constexpr int EPI = decltype(kEpi)::value;
+            constexpr bool C4 = decltype(kC4)::value != 0, RPART = decltype(kRpart)::value != 0;
+            constexpr bool FREE = EPI == 0 || EPI == 4;          // any channel count: lanes may hold channels that do not exist
+            constexpr bool LOAD_C = EPI != 0, LOAD_H = EPI == 2 || RPART, LOAD_Z = EPI == 2;
+            constexpr unsigned PXB = C4 ? 16u : 4u;              // bytes per pixel step
+            // address of channel cs + i (cs a multiple of 4) of an fp32 tensor; the lane adds `loff` bytes.  f32_at: wave-uniform
+            // and held, so that the access keeps the form scalar base + 32-bit lane offset (left to itself the compiler moves
+            // the lane offset into the base once per tile and adds the channel term with 64-bit vector arithmetic)
+            auto f32_lane = [&](const float *base, int cs, int i) -> const char * {
+                return (const char *)base + (C4 ? (long)(cs >> 2) * iHW * 16 : (long)(cs + i) * iHW * 4);
+            };
+            auto f32_at = [&](const float *base, int cs, int i) -> const char * { return c8_base(f32_lane(base, cs, i)); };
+            auto load4 = [&](const float *base, int cs, unsigned loff, float (&v)[4]) {
+                if constexpr (C4) {
+                    const float4 t = *(const float4 *)(f32_at(base, cs, 0) + loff);
+                    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+                } else {
 #pragma unroll
-        for (int m = 0; m < MF; ++m) {
-            float bv[16];                                      // this lane's 16 biases of block m
+                    for (int i = 0; i < 4; ++i) v[i] = *(const float *)(f32_at(base, cs, i) + loff);
+                }
+            };
+            auto load4_lane = [&](const float *base, int cs, unsigned loff, float (&v)[4]) {      // cs differs between lanes
+                if constexpr (C4) {
+                    const float4 t = *(const float4 *)(f32_lane(base, cs, 0) + loff);
+                    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+                } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co_w + m * 32 + 4 * kg + (r & 3) + 8 * (r >> 2);
-                bv[r] = a.bias ? a.bias[co < a.Cout ? co : a.Cout - 1] : 0.0f;
-            }
+                    for (int i = 0; i < 4; ++i) v[i] = *(const float *)(f32_lane(base, cs, i) + loff);
+                }
+            };
 #pragma unroll
-            for (int n = 0; n < NF; ++n) {
-                const int oh = h0 + wn * NF + n, ow = w0 + li;
-                const bool inside = oh < a.H && ow < a.W;
-                const long px = inside ? (long)oh * a.W + ow : 0;
-                // The fp32 operands of the fused epilogues (gate terms, state, residual) of all four channel groups of this
-                // accumulator block are fetched BEFORE the block's first store.  Interleaved with the stores, as they were, a
-                // group's loads waited behind the previous group's stores (a load cannot move above a store that may alias
-                // it): the epilogue was a chain of memory round trips -- counters of an epilogue-only launch: 57 % of the wave
-                // cycles in s_waitcnt (tools/c8_epi_pmc.sh) -- 32 per wave, 8 now.  The registers come from the next tile's
-                // prefetched fragments, which are re-read after the epilogue instead of being held across it.
-                float gca[4][4], gha[4][4], gza[4][4];
+            for (int m = 0; m < MF; ++m) {
+                float bv[16];                                      // this lane's 16 biases of block m
+                if (bias_p) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int cl = cw + m * 32 + 8 * j + 4 * kg;
-                    if (a.epi != 0) f32_load4(f32_ptr(pc, cl < cout_eff ? cl : 0, px, iHW), iHW, gca[j]);
-                    else gca[j][0] = gca[j][1] = gca[j][2] = gca[j][3] = 0.0f;
-                    if (ph) f32_load4(f32_ptr(ph, cl, px, iHW), iHW, gha[j]);
-                    else gha[j][0] = gha[j][1] = gha[j][2] = gha[j][3] = 0.0f;
-                    if (pz) f32_load4(f32_ptr(pz, cl, px, iHW), iHW, gza[j]);
-                    else gza[j][0] = gza[j][1] = gza[j][2] = gza[j][3] = 0.0f;
+                    for (int r = 0; r < 16; ++r) {
+                        const int cu = co_w + m * 32 + (r & 3) + 8 * (r >> 2);      // the lane's channel is cu + 4 kg
+                        if constexpr (FREE) {
+                            const int co = cu + 4 * kg;
+                            bv[r] = bias_p[co < Cout ? co : Cout - 1];
+                        } else bv[r] = ((const float *)((const char *)c8_base(bias_p + (cu & ~3)) + (unsigned)kg * 16u))[r & 3];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) bv[r] = 0.0f;
                 }
 #pragma unroll
-                for (int jp = 0; jp < 2; ++jp) {
-                    float v[2][4];
+                for (int n = 0; n < NF; ++n) {
+                    const int oh = h0 + wn * NF + n;               // wave-uniform
+                    const bool inside = oh < H && col_in;
+                    const unsigned px = inside ? (unsigned)(oh * W + ow) : 0u;
+                    const unsigned loff = kg_f32 + px * PXB;
+                    // The fp32 operands of the fused epilogues (gate terms, state, residual) of all four channel groups of this
+                    // accumulator block are fetched BEFORE the block's first store.  Interleaved with the stores, as they were, a
+                    // group's loads waited behind the previous group's stores (a load cannot move above a store that may alias
+                    // it): the epilogue was a chain of memory round trips -- counters of an epilogue-only launch: 57 % of the wave
+                    // cycles in s_waitcnt (tools/c8_epi_pmc.sh) -- 32 per wave, 8 now.  The registers come from the next tile's
+                    // prefetched fragments, which are re-read after the epilogue instead of being held across it.
+                    float gca[4][4], gha[4][4], gza[4][4];
 #pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        const int j = 2 * jp + jj;
-                        const int cl = cw + m * 32 + 8 * j + 4 * kg;           // first of this lane's 4 channels (destination numbering)
-                        float x[4];
+                    for (int j = 0; j < 4; ++j) {
+                        const int cs = cw + m * 32 + 8 * j;        // the lane's 4 channels start at cs + 4 kg
+                        if constexpr (LOAD_C) {
+                            if (FREE && cs + 8 > Ch) {             // channels past the layer's last read channel 0 (and are not used)
+                                const bool ok = cs + 4 * kg < Ch;
+                                load4_lane(pc, ok ? cs : 0, ok ? loff : px * PXB, gca[j]);
+                            } else load4(pc, cs, loff, gca[j]);
+                        }
+                        if constexpr (LOAD_H) load4(ph, cs, loff, gha[j]);
+                        if constexpr (LOAD_Z) load4(pz, cs, loff, gza[j]);
+                    }
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) x[i] = acc[m][n][4 * j + i] * a.out_scale + bv[4 * j + i];
-                        if (a.epi == 0) {
+                    for (int jp = 0; jp < 2; ++jp) {
+                        float v[2][4];
+#pragma unroll
+                        for (int jj = 0; jj < 2; ++jj) {
+                            const int j = 2 * jp + jj;
+                            const int cs = cw + m * 32 + 8 * j;
+                            const int cl = cs + 4 * kg;            // first of this lane's 4 channels (destination numbering)
+                            const bool rag = FREE && cs + 8 > Ch;  // wave-uniform: this group reaches past the last channel
 #pragma unroll
                             for (int i = 0; i < 4; ++i) {
-                                float y = a.relu ? dkt_relu(x[i]) : x[i];
-                                if (cl + i >= a.Cout) {
-                                    y = 0.0f;
-                                    if (a.tail && cl + i < a.Cout + a.tail_ch && inside)
-                                        y = a.tail[(long)b * a.tail_bs + (long)(cl + i - a.Cout) * iHW + px] * a.tail_ratio;
-                                }
-                                v[jj][i] = y;
-                            }
-                        } else {
-                            float gc[4], gh[4], gz[4];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                gc[i] = gca[j][i];
-                                gh[i] = gha[j][i];
-                                gz[i] = gza[j][i];
-                            }
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                if (a.epi == 1) {
-                                    const float g = c8_sigmoid(__fadd_rn(x[i], gc[i]));
-                                    v[jj][i] = rpart ? __fmul_rn(g, gh[i]) : g;
-                                } else if (a.epi == 4) {
+                                const float x = acc[m][n][4 * j + i] * out_scale + bv[4 * j + i];
+                                if constexpr (EPI == 0) {
+                                    v[jj][i] = relu ? dkt_relu(x) : x;
+                                } else if constexpr (EPI == 1) {
+                                    const float g = c8_sigmoid(__fadd_rn(x, gca[j][i]));
+                                    v[jj][i] = RPART ? __fmul_rn(g, gha[j][i]) : g;
+                                } else if constexpr (EPI == 4) {
                                     // residual join of core/extractor.py:52-60: relu(x + [relu](conv + bias)); padded channels stay 0
-                                    const float t = a.relu ? dkt_relu(x[i]) : x[i];
-                                    v[jj][i] = cl < a.Cout ? dkt_relu(__fadd_rn(gc[i], t)) : 0.0f;
+                                    const float t = relu ? dkt_relu(x) : x;
+                                    v[jj][i] = dkt_relu(__fadd_rn(gca[j][i], t));
                                 } else {
-                                    const float q = c8_tanh(__fadd_rn(x[i], gc[i]));
-                                    v[jj][i] = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, gz[i]), gh[i]), __fmul_rn(gz[i], q));
+                                    const float q = c8_tanh(__fadd_rn(x, gca[j][i]));
+                                    v[jj][i] = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, gza[j][i]), gha[j][i]), __fmul_rn(gza[j][i], q));
+                                }
+                            }
+                            if constexpr (FREE) {
+                                if (rag) {
+#pragma unroll
+                                    for (int i = 0; i < 4; ++i) {
+                                        if (cl + i >= Cout) {
+                                            float y = 0.0f;
+                                            if constexpr (EPI == 0) {      // (tail_ch is 0 where the layer has no tail)
+                                                if (cl + i < Cout + tail_ch && inside) y = ptail[(long)(cl + i - Cout) * iHW + px] * tail_ratio;
+                                            }
+                                            v[jj][i] = y;
+                                        }
+                                    }
+                                }
+                            }
+                            if (po) {                              // (wave-uniform, per group of four values)
+                                if constexpr (C4) {                // (C4 tensors are padded to 4 channels)
+                                    if (inside && (!FREE || cl < Ch))
+                                        *(float4 *)(const_cast<char *>(f32_at(po, cs, 0)) + loff) = make_float4(v[jj][0], v[jj][1], v[jj][2], v[jj][3]);
+                                } else {
+#pragma unroll
+                                    for (int i = 0; i < 4; ++i)
+                                        if (inside && (!FREE || cl + i < Ch)) *(float *)(const_cast<char *>(f32_at(po, cs, i)) + loff) = v[jj][i];
                                 }
                             }
                         }
-                        if (po && inside && cl < cout_eff)
-                            f32_store4(const_cast<float *>(f32_ptr(po, cl, px, iHW)), iHW, v[jj], cout_eff - cl);
+                        if (pc8) {
+                            // C8S: c8_split_pair completes the pair of groups to 8 consecutive channels per 16 bytes, after which the
+                            // lane stores group 2 jp + kg of its block
+                            u32x4 hi, lo;
+                            c8_split_pair(v[0], v[1], act_scale, hi, lo);
+                            const int gs = c8_g0 + m * 4 + 2 * jp;     // wave-uniform; the lane's group is gs + kg
+                            // (groups past the destination's padded channel count do not exist)
+                            if (inside && (!FREE || gs + kg < c8_gend)) {
+                                char *const p = pc8 + (long)gs * 2 * c8_plane;
+                                const unsigned off = kg_c8 + (unsigned)((oh + 1) * c8_Wp + (ow + 1)) * 16u;
+                                *(u32x4 *)(c8_base(p) + off) = hi;
+                                *(u32x4 *)(c8_base(p + c8_plane) + off) = lo;
+                            }
+                        }
                     }
-                    if (pc8) store_c8_pair(pc8, c8_ch0 + cw + m * 32, c8_gend, jp, oh, ow, inside, v[0], v[1]);
                 }
             }
-        }
+        };
+        // ---- the one dispatch of the tile
+        constexpr C8Tag<0> k0{};
+        constexpr C8Tag<1> k1{};
+        constexpr C8Tag<2> k2{};
+        constexpr C8Tag<4> k4{};
+        auto by_c4 = [&](auto kEpi, auto kRpart) __attribute__((always_inline)) {
+            if (c4) body(kEpi, k1, kRpart);
+            else body(kEpi, k0, kRpart);
+        };
+        if (epi == 0) by_c4(k0, k0);
+        else if (epi == 1) {
+            if (rpart) by_c4(k1, k1);
+            else by_c4(k1, k0);
+        } else if (epi == 2) by_c4(k2, k0);
+        else by_c4(k4, k0);
     };
 
     // ------------------------------------------------------------------------------------------------
@@ -466,9 +580,104 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : 2)) void conv_c8_k
     conv_c8_body<WM, WN, NF, RING, PASSES>(ap, nb0, (int)gridDim.x, (int)blockIdx.x, lds);
 }
 
+// ---- launch
+template <int WM, int WN, int NF, int RING, int PASSES = 3>
+static int c8_launch(C8Args a, int B, hipStream_t st, const C8Args *second, int B2) {
+    constexpr int NW = WM * WN, TR = WN * NF;
+    constexpr int NU = (TR + 2) * C8_PC * 4;
+    constexpr int NPR = (NU + 63) / 64, NIA = (NPR + NW - 1) / NW;
+    size_t lds = (size_t)2 * (NIA * NW > NPR ? NPR + 1 : NPR) * 1024 + (size_t)RING * WM * 4096;
+    const bool head = a.epi == 3 || (second && second->epi == 3);
+    if (head) {
+        if (NW != 8) return DKT_E_UNSUPPORTED;                // one block per CU: the extra LDS costs no residency
+        lds += (size_t)NW * NF * 9 * 32 * 4;
+    }
+    auto kern = conv_c8_kernel<WM, WN, NF, RING, PASSES>;
+    static int slots[64] = {0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (!slots[dev & 63]) {
+        size_t want = lds + (NW == 8 && !head ? (size_t)NW * NF * 9 * 32 * 4 : 0);     // (room for a later head launch of this shape)
+        if (want > 160 * 1024) want = lds;
+        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
+        if (e != hipSuccess) return (int)e;
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * NW, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+        slots[dev & 63] = per_cu * cus;
+    }
+    auto shape = [&](C8Args &x, int nb) -> long {
+        x.tiles_w = (x.W + 31) / 32;
+        x.tiles_xy = x.tiles_w * ((x.H + TR - 1) / TR);
+        x.n_co = (x.n_co64 + WM - 1) / WM;
+        const long total = (long)x.tiles_xy * x.n_co * nb;
+        x.total_tiles = (int)total;
+        return total;
+    };
+    const long cap = slots[dev & 63];
+    C8ArgsPair ap;
+    const long total0 = shape(a, B);
+    if (total0 > 0x7fffffffL) return DKT_E_SHAPE;
+    ap.p[0] = a;
+    ap.p[1] = a;
+    long nb0 = total0 > cap ? cap : total0, nb1 = 0;
+    if (second) {
+        C8Args b = *second;
+        const long total1 = shape(b, B2);
+        if (total1 > 0x7fffffffL) return DKT_E_SHAPE;
+        ap.p[1] = b;
+        nb0 = total0; nb1 = total1;
+        if (total0 + total1 > cap) {
+            const double w0 = (double)total0 * a.nchunks, w1 = (double)total1 * b.nchunks;
+            nb1 = (long)(cap * w1 / (w0 + w1) + 0.5);
+            nb1 = nb1 < 1 ? 1 : (nb1 > total1 ? total1 : nb1);
+            nb0 = cap - nb1;
+            if (nb0 > total0) nb0 = total0;
+            if (nb0 < 1) nb0 = 1;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nb0 + nb1)), dim3(64 * NW), lds, st, ap, (int)nb0);
+    return dkt_launch_status();
+}
+
+
+// cfg: 0 = by shape; 1: 256 co x 8 rows (8 waves); 2: 128 co x 8 rows (8 waves); 3: 64 co x 8 rows (4 waves, two blocks per CU);
+//      4: 64 co x 4 rows (4 waves); 5: 256 co x 4 rows (4 waves, two blocks per CU); 6: 128 co x 8 rows (4 waves, two blocks per CU)
+template <int PASSES>
+int c8_dispatch_p(const C8Args &a, int B, int cfg, hipStream_t st, const C8Args *second, int B2) {
+    switch (cfg) {
+    case 1: return c8_launch<4, 2, 4, 4, PASSES>(a, B, st, second, B2);
+    case 2: return c8_launch<2, 4, 2, 4, PASSES>(a, B, st, second, B2);
+    case 3: return c8_launch<1, 4, 2, 6, PASSES>(a, B, st, second, B2);
+    case 4: return c8_launch<1, 4, 1, 8, PASSES>(a, B, st, second, B2);
+    default: break;
+    }
+    if constexpr (PASSES == 3) {          // (the 4-wave forms kept for the tests exist at full precision only)
+        if (cfg == 5) return c8_launch<4, 1, 4, 3>(a, B, st, second, B2);
+        if (cfg == 6) return c8_launch<2, 2, 4, 4>(a, B, st, second, B2);
+    }
+    return DKT_E_UNSUPPORTED;
+}
+
+#if C8_TU == -1 || C8_TU == 1
+template int c8_dispatch_p<1>(const C8Args &, int, int, hipStream_t, const C8Args *, int);
+#endif
+#if C8_TU == -1 || C8_TU == 2
+template int c8_dispatch_p<2>(const C8Args &, int, int, hipStream_t, const C8Args *, int);
+#endif
+#if C8_TU == -1 || C8_TU == 3
+template int c8_dispatch_p<3>(const C8Args &, int, int, hipStream_t, const C8Args *, int);
+#endif
+#endif      // C8_TU != 0
+
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
+#if C8_TU <= 0
+// (defined in the units that hold the kernel)
+template <int PASSES>
+int c8_dispatch_p(const C8Args &a, int B, int cfg, hipStream_t st, const C8Args *second, int B2);
+
 static int c8_round(int x, int m) { return (x + m - 1) / m * m; }
 
 extern "C" int dkt_act_c8_dims(int H, int W, int *Hp, int *Wp) {
@@ -611,65 +820,6 @@ extern "C" int dkt_conv_c8_pack_weights(const float *w, const int *src_channels,
     return dkt_launch_status();
 }
 
-// ---- launch
-template <int WM, int WN, int NF, int RING, int PASSES = 3>
-static int c8_launch(C8Args a, int B, hipStream_t st, const C8Args *second, int B2) {
-    constexpr int NW = WM * WN, TR = WN * NF;
-    constexpr int NU = (TR + 2) * C8_PC * 4;
-    constexpr int NPR = (NU + 63) / 64, NIA = (NPR + NW - 1) / NW;
-    size_t lds = (size_t)2 * (NIA * NW > NPR ? NPR + 1 : NPR) * 1024 + (size_t)RING * WM * 4096;
-    const bool head = a.epi == 3 || (second && second->epi == 3);
-    if (head) {
-        if (NW != 8) return DKT_E_UNSUPPORTED;                // one block per CU: the extra LDS costs no residency
-        lds += (size_t)NW * NF * 9 * 32 * 4;
-    }
-    auto kern = conv_c8_kernel<WM, WN, NF, RING, PASSES>;
-    static int slots[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!slots[dev & 63]) {
-        size_t want = lds + (NW == 8 && !head ? (size_t)NW * NF * 9 * 32 * 4 : 0);     // (room for a later head launch of this shape)
-        if (want > 160 * 1024) want = lds;
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
-        if (e != hipSuccess) return (int)e;
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * NW, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        slots[dev & 63] = per_cu * cus;
-    }
-    auto shape = [&](C8Args &x, int nb) -> long {
-        x.tiles_w = (x.W + 31) / 32;
-        x.tiles_xy = x.tiles_w * ((x.H + TR - 1) / TR);
-        x.n_co = (x.n_co64 + WM - 1) / WM;
-        const long total = (long)x.tiles_xy * x.n_co * nb;
-        x.total_tiles = (int)total;
-        return total;
-    };
-    const long cap = slots[dev & 63];
-    C8ArgsPair ap;
-    const long total0 = shape(a, B);
-    if (total0 > 0x7fffffffL) return DKT_E_SHAPE;
-    ap.p[0] = a;
-    ap.p[1] = a;
-    long nb0 = total0 > cap ? cap : total0, nb1 = 0;
-    if (second) {
-        C8Args b = *second;
-        const long total1 = shape(b, B2);
-        if (total1 > 0x7fffffffL) return DKT_E_SHAPE;
-        ap.p[1] = b;
-        nb0 = total0; nb1 = total1;
-        if (total0 + total1 > cap) {
-            const double w0 = (double)total0 * a.nchunks, w1 = (double)total1 * b.nchunks;
-            nb1 = (long)(cap * w1 / (w0 + w1) + 0.5);
-            nb1 = nb1 < 1 ? 1 : (nb1 > total1 ? total1 : nb1);
-            nb0 = cap - nb1;
-            if (nb0 > total0) nb0 = total0;
-            if (nb0 < 1) nb0 = 1;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nb0 + nb1)), dim3(64 * NW), lds, st, ap, (int)nb0);
-    return dkt_launch_status();
-}
 
 static int c8_fill(C8Args &a, const dkt_conv_c8_desc *d) {
     if (!d) return DKT_E_NULL;
@@ -725,24 +875,6 @@ static int c8_fill(C8Args &a, const dkt_conv_c8_desc *d) {
     if (a.tail && (a.epi != 0 || !a.out_c8 || a.tail_ch <= 0 || a.Cout + a.tail_ch > a.n_co64 * 64)) return DKT_E_UNSUPPORTED;
     a.tiles_w = a.tiles_xy = a.n_co = a.total_tiles = 0;
     return DKT_OK;
-}
-
-// cfg: 0 = by shape; 1: 256 co x 8 rows (8 waves); 2: 128 co x 8 rows (8 waves); 3: 64 co x 8 rows (4 waves, two blocks per CU);
-//      4: 64 co x 4 rows (4 waves); 5: 256 co x 4 rows (4 waves, two blocks per CU); 6: 128 co x 8 rows (4 waves, two blocks per CU)
-template <int PASSES>
-static int c8_dispatch_p(const C8Args &a, int B, int cfg, hipStream_t st, const C8Args *second, int B2) {
-    switch (cfg) {
-    case 1: return c8_launch<4, 2, 4, 4, PASSES>(a, B, st, second, B2);
-    case 2: return c8_launch<2, 4, 2, 4, PASSES>(a, B, st, second, B2);
-    case 3: return c8_launch<1, 4, 2, 6, PASSES>(a, B, st, second, B2);
-    case 4: return c8_launch<1, 4, 1, 8, PASSES>(a, B, st, second, B2);
-    default: break;
-    }
-    if constexpr (PASSES == 3) {          // (the 4-wave forms kept for the tests exist at full precision only)
-        if (cfg == 5) return c8_launch<4, 1, 4, 3>(a, B, st, second, B2);
-        if (cfg == 6) return c8_launch<2, 2, 4, 4>(a, B, st, second, B2);
-    }
-    return DKT_E_UNSUPPORTED;
 }
 
 static int c8_dispatch(const C8Args &a, int B, int cfg, int passes, hipStream_t st, const C8Args *second, int B2) {
@@ -833,4 +965,4 @@ extern "C" int dkt_conv2d_c8_head_blocks(int Cout, int cfg) {
     if (cfg == 1) return (n64 + 3) / 4;
     return DKT_E_UNSUPPORTED;
 }
-
+#endif      // C8_TU <= 0

@@ -45,7 +45,7 @@ def main():
     path = write_variant(B, open(os.path.join(B.CSRC, "conv_c8.hip")).read(), subs, "conv_c8_%s" % tag)
     obj = os.path.join(OUT, "conv_c8_%s.o" % tag)
     subprocess.check_call([B.HIPCC] + B.CFLAGS + B.EXTRA_FLAGS["conv_c8"] + ["-I", B.CSRC, "-c", path, "-o", obj])
-    objs = [os.path.join(B.OBJ_DIR, f) for f in sorted(os.listdir(B.OBJ_DIR)) if f.endswith(".o") and f != "conv_c8.o"]
+    objs = [os.path.join(B.OBJ_DIR, f) for f in sorted(os.listdir(B.OBJ_DIR)) if f.endswith(".o") and not f.startswith("conv_c8")]
     lib = os.path.join(OUT, "libdktstereo_c8%s.so" % tag)
     subprocess.check_call([B.HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", obj] + objs + ["-o", lib])
     print(lib)
