@@ -310,6 +310,11 @@ def check(rc, what):
         names.append(what)
 
 
+def ptr(t):
+    """The address of an optional tensor: None (a null pointer) for None."""
+    return None if t is None else t.data_ptr()
+
+
 def ptr_array(tensors):
     arr = (ctypes.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):

@@ -21,8 +21,10 @@
 // tile-with-halo launch: a halo means reading the halo pixels' mask again (+16 % of the dominant traffic for a 64 x 16
 // tile), the workspace round trip is 2 * 9 * Dout floats per coarse pixel against the 2 * 9 f^2 of mask and gmask (6 %
 // at f = 4, Dout = 1), and no shape needs a special case.
+// The softmax, the taps, the row accesses, the meeting of the row sums and the second launch are the nine-tap core of
+// ups9.h, shared with context_upsample_train.hip; here are the two kernels that read the mask in its own layout.
 // Plain scalar fp32 (no packed math: DESIGN 3.4).
-#include "dkt_common.h"
+#include "ups9.h"
 
 #define UPS_DC 2                        // channels one pass keeps in registers (RAFT: D = 2, training Dout = 1)
 
@@ -32,104 +34,10 @@ __device__ __forceinline__ void ups_load9(const float *__restrict__ mp, long kst
     for (int k = 0; k < 9; ++k) m[k] = mp[(long)k * kstride];
 }
 
-// The softmax of dkt_convex_upsample (upsample.hip) in place, the same bits: max, expf(m - max), the sum in ascending k,
-// nine IEEE divisions.  The divisions are the compiler's own sequence for a / b (reciprocal estimate, one Newton step on
-// it, the quotient and two fused corrections) written out, so that the steps that depend on the divisor alone are done
-// once for the nine quotients.  The compiler's sequence differs from this one only by v_div_scale / v_div_fixup, which
-// leave the operands and the result as they are unless the divisor or the quotient is near the ends of the exponent
-// range: here 1 <= sum <= 9 (the largest logit contributes exactly 1), so that happens only for a numerator below 2^-103,
-// and every numerator below 2^-100 other than 0 takes the plain division.
-__device__ __forceinline__ void ups_softmax(float (&m)[9]) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) mx = fmaxf(mx, m[k]);
-    float sum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        m[k] = expf(__fsub_rn(m[k], mx));
-        sum = __fadd_rn(sum, m[k]);
-    }
-    const float r0 = __builtin_amdgcn_rcpf(sum);
-    const float r = __fmaf_rn(__fmaf_rn(-sum, r0, 1.0f), r0, r0);
-    bool tiny = false;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) tiny |= m[k] < 0x1p-100f && m[k] != 0.0f;
-    if (__builtin_expect(tiny, 0)) {                                        // a spread of the logits beyond 69
-#pragma unroll
-        for (int k = 0; k < 9; ++k) m[k] = __fdiv_rn(m[k], sum);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-        const float a = m[k];
-        float q = __fmul_rn(a, r);
-        q = __fmaf_rn(__fmaf_rn(-sum, q, a), r, q);
-        m[k] = __fmaf_rn(__fmaf_rn(-sum, q, a), r, q);
-    }
-}
-
 // v_{d,k} of one coarse pixel; fp = flow + (n*D + d)*H*W
 __device__ __forceinline__ float ups_tap(const float *__restrict__ fp, int h, int w, int k, int H, int W, float ff) {
     const int hh = h + k / 3 - 1, ww = w + k % 3 - 1;
     return (hh >= 0 && hh < H && ww >= 0 && ww < W) ? __fmul_rn(ff, fp[(long)hh * W + ww]) : 0.0f;
-}
-
-// v_{d,k} of one coarse pixel for the channels d[0..UPS_DC) of image n (fn = flow + n*D*H*W), in two steps: the loads,
-// unconditional (clamped index) so that all 9 * UPS_DC are in flight together with the mask loads the caller issues
-// next, and the finish (zero padding as a select, the factor; channels that are not `on` give 0).  (Left to itself the
-// compiler sinks each load under its bounds test: one branch and one full wait per tap.  The empty asm of the finish
-// makes each loaded value count as used where it stands.)
-__device__ __forceinline__ void ups_taps_load(const float *__restrict__ fn, long HW, const int (&d)[UPS_DC], int h, int w, int H,
-                                              int W, float (&x)[UPS_DC][9]) {
-#pragma unroll
-    for (int dd = 0; dd < UPS_DC; ++dd)
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            x[dd][k] = fn[d[dd] * HW + (long)min(max(h + k / 3 - 1, 0), H - 1) * W + min(max(w + k % 3 - 1, 0), W - 1)];
-}
-
-__device__ __forceinline__ void ups_taps_finish(float (&x)[UPS_DC][9], const bool (&on)[UPS_DC], int h, int w, int H, int W,
-                                                float ff) {
-#pragma unroll
-    for (int dd = 0; dd < UPS_DC; ++dd)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) asm volatile("" : "+v"(x[dd][k]));
-#pragma unroll
-    for (int dd = 0; dd < UPS_DC; ++dd)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int hh = h + k / 3 - 1, ww = w + k % 3 - 1;
-            x[dd][k] = (on[dd] && hh >= 0 && hh < H && ww >= 0 && ww < W) ? __fmul_rn(ff, x[dd][k]) : 0.0f;
-        }
-}
-
-template <int F>
-__device__ __forceinline__ void ups_load_row(const float *__restrict__ p, float (&v)[F]) {
-    if constexpr (F == 1) {
-        v[0] = p[0];
-    } else if constexpr (F == 2) {
-        const float2 t = *reinterpret_cast<const float2 *>(p);
-        v[0] = t.x, v[1] = t.y;
-    } else {
-#pragma unroll
-        for (int q = 0; q < F / 4; ++q) {
-            const float4 t = reinterpret_cast<const float4 *>(p)[q];
-            v[4 * q] = t.x, v[4 * q + 1] = t.y, v[4 * q + 2] = t.z, v[4 * q + 3] = t.w;
-        }
-    }
-}
-
-template <int F>
-__device__ __forceinline__ void ups_store_row(float *__restrict__ p, const float (&v)[F]) {
-    if constexpr (F == 1) {
-        p[0] = v[0];
-    } else if constexpr (F == 2) {
-        *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-    } else {
-#pragma unroll
-        for (int q = 0; q < F / 4; ++q)
-            reinterpret_cast<float4 *>(p)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    }
 }
 
 // block (64 * F): wave i = fine row i of 64 consecutive coarse pixels of image blockIdx.y; channels [d0, d0 + UPS_DC)
@@ -137,7 +45,7 @@ template <int F>
 __global__ __launch_bounds__(64 * F) void ups_fwd_kernel(const float *__restrict__ flow, const float *__restrict__ mask,
                                                          float *__restrict__ out, int D, int Dout, int d0, int H, int W) {
     const long HW = (long)H * W;
-    const int p = blockIdx.x * 64 + (threadIdx.x & 63);                    // H * W < 2^31 (ups_check)
+    const int p = blockIdx.x * 64 + (threadIdx.x & 63);                    // H * W < 2^31 (ups9_check)
     if (p >= HW) return;
     const int i = threadIdx.x >> 6, n = blockIdx.y;
     const int h = p / W, w = p - h * W;
@@ -146,16 +54,16 @@ __global__ __launch_bounds__(64 * F) void ups_fwd_kernel(const float *__restrict
     bool on[UPS_DC];
 #pragma unroll
     for (int dd = 0; dd < UPS_DC; ++dd) on[dd] = d0 + dd < Dout, dch[dd] = min(d0 + dd, Dout - 1);
-    ups_taps_load(flow + (long)n * D * HW, HW, dch, h, w, H, W, v);
+    ups9_taps_load<UPS_DC>(flow + (long)n * D * HW, HW, dch, h, w, H, W, v);
     const float *mp = mask + ((long)n * 9 * F * F + (long)i * F) * HW + p;
     float mm[F][9];
 #pragma unroll
     for (int j = 0; j < F; ++j) ups_load9(mp + (long)j * HW, (long)F * F * HW, mm[j]);
-    ups_taps_finish(v, on, h, w, H, W, (float)F);
+    ups9_taps_finish<UPS_DC>(v, on, h, w, H, W, (float)F);
 #pragma unroll
     for (int j = 0; j < F; ++j) {
         float (&m)[9] = mm[j];
-        ups_softmax(m);
+        ups9_softmax(m);
 #pragma unroll
         for (int dd = 0; dd < UPS_DC; ++dd) {
             float a = 0.0f;
@@ -167,7 +75,7 @@ __global__ __launch_bounds__(64 * F) void ups_fwd_kernel(const float *__restrict
 #pragma unroll
     for (int dd = 0; dd < UPS_DC; ++dd)
         if (d0 + dd < Dout)
-            ups_store_row<F>(out + ((((long)n * Dout + d0 + dd) * H + h) * F + i) * ((long)W * F) + (long)w * F, acc[dd]);
+            ups9_store_row<F>(out + ((((long)n * Dout + d0 + dd) * H + h) * F + i) * ((long)W * F) + (long)w * F, acc[dd]);
 }
 
 // Same mapping.  gmask (when non-null; only the pass with d0 == 0 gets it) needs every channel of a_k: the pass's own
@@ -181,7 +89,7 @@ __global__ __launch_bounds__(64 * F) void ups_bwd_kernel(const float *__restrict
     __shared__ float red[F][UPS_DC * 9][64];
     const long HW = (long)H * W;
     const int lane = threadIdx.x & 63, i = threadIdx.x >> 6, n = blockIdx.y;
-    const int p = blockIdx.x * 64 + lane;                                  // H * W < 2^31 (ups_check)
+    const int p = blockIdx.x * 64 + lane;                                  // H * W < 2^31 (ups9_check)
     const bool live = p < HW;
     const long Wf = (long)W * F, Hf = (long)H * F;
     float c[UPS_DC][9];
@@ -197,14 +105,14 @@ __global__ __launch_bounds__(64 * F) void ups_bwd_kernel(const float *__restrict
         bool on[UPS_DC];
 #pragma unroll
         for (int dd = 0; dd < UPS_DC; ++dd) on[dd] = d0 + dd < Dout, dch[dd] = min(d0 + dd, Dout - 1);
-        ups_taps_load(flow + (long)n * D * HW, HW, dch, h, w, H, W, v);
+        ups9_taps_load<UPS_DC>(flow + (long)n * D * HW, HW, dch, h, w, H, W, v);
 #pragma unroll
-        for (int dd = 0; dd < UPS_DC; ++dd) ups_load_row<F>(gp + (long)dch[dd] * Hf * Wf, g[dd]);
+        for (int dd = 0; dd < UPS_DC; ++dd) ups9_load_row<F>(gp + (long)dch[dd] * Hf * Wf, g[dd]);
         const long cbase = ((long)n * 9 * F * F + (long)i * F) * HW + p;
         float mm[F][9];
 #pragma unroll
         for (int j = 0; j < F; ++j) ups_load9(mask + cbase + (long)j * HW, (long)F * F * HW, mm[j]);
-        ups_taps_finish(v, on, h, w, H, W, (float)F);
+        ups9_taps_finish<UPS_DC>(v, on, h, w, H, W, (float)F);
 #pragma unroll
         for (int dd = 0; dd < UPS_DC; ++dd)
             if (!on[dd]) {
@@ -214,7 +122,7 @@ __global__ __launch_bounds__(64 * F) void ups_bwd_kernel(const float *__restrict
 #pragma unroll
         for (int j = 0; j < F; ++j) {
             float (&m)[9] = mm[j];
-            ups_softmax(m);
+            ups9_softmax(m);
             if (gmask) {
                 float a[9];
 #pragma unroll
@@ -245,63 +153,26 @@ __global__ __launch_bounds__(64 * F) void ups_bwd_kernel(const float *__restrict
         }
     }
     if (!ws) return;                                                        // uniform: a launch argument
-#pragma unroll
-    for (int dd = 0; dd < UPS_DC; ++dd)
-#pragma unroll
-        for (int k = 0; k < 9; ++k) red[i][dd * 9 + k][lane] = c[dd][k];
-    __syncthreads();
-    for (int e = threadIdx.x; e < UPS_DC * 9 * 64; e += 64 * F) {
-        const int q = e >> 6, l = e & 63, dd = q / 9, k = q - dd * 9;
-        const int pp = blockIdx.x * 64 + l;
-        if (d0 + dd >= Dout || pp >= HW) continue;
-        float s = red[0][q][l];
-#pragma unroll
-        for (int r = 1; r < F; ++r) s = __fadd_rn(s, red[r][q][l]);
-        ws[(((long)n * Dout + d0 + dd) * 9 + k) * HW + pp] = s;
-    }
+    ups9_reduce_rows<F, UPS_DC>(red, c, i, lane, ws, n, Dout, d0, HW);      // every thread comes here: no return above but that one
 }
 
-// thread = one gflow element of plane (blockIdx.z, blockIdx.y) = (n, d); channels d >= Dout get an exact 0
-__global__ __launch_bounds__(256) void ups_gflow_kernel(const float *__restrict__ ws, float *__restrict__ gflow, int Dout,
-                                                        int H, int W, float ff) {
-    const int HW = H * W, D = gridDim.y, d = blockIdx.y, n = blockIdx.z;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= HW) return;
-    const int y = p / W, x = p - y * W;
-    float s = 0.0f;
-    if (d < Dout) {                                                         // uniform
-        const float *cp = ws + ((long)n * Dout + d) * 9 * HW;
-        float t[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {                                       // clamped loads, the padding a select
-            const int hh = y - k / 3 + 1, ww = x - k % 3 + 1;
-            t[k] = cp[(long)k * HW + min(max(hh, 0), H - 1) * W + min(max(ww, 0), W - 1)];
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int hh = y - k / 3 + 1, ww = x - k % 3 + 1;
-            if (hh >= 0 && hh < H && ww >= 0 && ww < W) s = __fadd_rn(s, t[k]);
-        }
-        s = __fmul_rn(ff, s);
-    }
-    gflow[((long)n * D + d) * HW + p] = s;
-}
-
+// every sign before every limit
 static int ups_check(int N, int D, int Dout, int H, int W, int factor) {
-    if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || factor < 1 || Dout < 1 || Dout > D) return DKT_E_SHAPE;
-    if (factor != 1 && factor != 2 && factor != 4 && factor != 8) return DKT_E_UNSUPPORTED;
-    if (N > 65535 || D > 65535 || (long)H * W > 0x7fffffffL - 256) return DKT_E_UNSUPPORTED;   // (pixel indices are int)
+    if (D <= 0 || factor < 1 || Dout < 1 || Dout > D) return DKT_E_SHAPE;
+    const int rc = ups9_check(N, H, W);
+    if (rc != DKT_OK) return rc;
+    if ((factor != 1 && factor != 2 && factor != 4 && factor != 8) || D > 65535) return DKT_E_UNSUPPORTED;
     return DKT_OK;
 }
 
 // rows of f floats are moved as one access of min(4 f, 16) bytes
 static bool ups_aligned(const void *p, int factor) {
-    return (uintptr_t)p % (size_t)(factor >= 4 ? 16 : 4 * factor) == 0;
+    return ups9_aligned(p, factor >= 4 ? 16 : 4 * factor);
 }
 
 template <int F>
 static void ups_fwd_launch(const float *flow, const float *mask, float *out, int N, int D, int Dout, int H, int W, hipStream_t st) {
-    const dim3 grid((unsigned)(((long)H * W + 63) / 64), (unsigned)N);
+    const dim3 grid = ups9_grid(N, H, W);
     for (int d0 = 0; d0 < Dout; d0 += UPS_DC)
         hipLaunchKernelGGL(ups_fwd_kernel<F>, grid, dim3(64 * F), 0, st, flow, mask, out, D, Dout, d0, H, W);
 }
@@ -326,7 +197,7 @@ extern "C" int dkt_convex_upsample_fwd(const float *flow, const float *mask, flo
 template <int F>
 static void ups_bwd_launch(const float *gout, long gbs, const float *flow, const float *mask, float *gmask, float *ws,
                            int N, int D, int Dout, int H, int W, hipStream_t st) {
-    const dim3 grid((unsigned)(((long)H * W + 63) / 64), (unsigned)N);
+    const dim3 grid = ups9_grid(N, H, W);
     // without a workspace (no flow gradient asked for) one pass gives gmask; with one, a pass per UPS_DC channels
     for (int d0 = 0; d0 < (ws ? Dout : 1); d0 += UPS_DC) {
         if (Dout > UPS_DC)
@@ -355,8 +226,6 @@ extern "C" int dkt_convex_upsample_bwd(const float *gout, long gout_bstride, con
     case 4: ups_bwd_launch<4>(gout, gout_bstride, flow, mask, gmask, w, N, D, Dout, H, W, st); break;
     default: ups_bwd_launch<8>(gout, gout_bstride, flow, mask, gmask, w, N, D, Dout, H, W, st); break;
     }
-    if (gflow)
-        hipLaunchKernelGGL(ups_gflow_kernel, dim3((unsigned)(((long)H * W + 255) / 256), (unsigned)D, (unsigned)N), dim3(256), 0, st,
-                           ws, gflow, Dout, H, W, (float)factor);
+    if (gflow) ups9_gather(ws, gflow, N, D, Dout, H, W, (float)factor, st);
     return dkt_launch_status();
 }

@@ -24,10 +24,6 @@ def _strided(t):
     return t, C * H * W
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _require_f32(*tensors):
     _ffi.require_gpu(*tensors)
     for t in tensors:
@@ -68,7 +64,8 @@ class _GateZrFn(torch.autograd.Function):
         gazr = torch.empty((B, 2 * Ch, H, W), device=z.device, dtype=torch.float32) if need_a else None
         gh = torch.empty_like(z) if need_h else None
         rc = _ffi.lib().dkt_gru_gate_zr_bwd(gz.data_ptr(), grh.data_ptr(), grh_bs, z.data_ptr(), r.data_ptr(), h.data_ptr(),
-                                            ctx.h_bs, _ptr(gazr), _ptr(gh), B, Ch, H * W, _ffi.device_of(z), _ffi.stream_of(z))
+                                            ctx.h_bs, _ffi.ptr(gazr), _ffi.ptr(gh), B, Ch, H * W,
+                                            _ffi.device_of(z), _ffi.stream_of(z))
         _ffi.check(rc, "dkt_gru_gate_zr_bwd")
         na, ncz, ncr = ctx.needs_input_grad[:3]
         # the gradients of cz and cr are the halves of gazr: views, no further writes
@@ -107,7 +104,8 @@ class _GateOutFn(torch.autograd.Function):
         gz = torch.empty_like(z) if nz else None
         gh = torch.empty_like(z) if nh else None
         rc = _ffi.lib().dkt_gru_gate_out_bwd(gout.data_ptr(), g_bs, z.data_ptr(), q.data_ptr(), h.data_ptr(), ctx.h_bs,
-                                             _ptr(gaq), _ptr(gz), _ptr(gh), B, Ch, H * W, _ffi.device_of(z), _ffi.stream_of(z))
+                                             _ffi.ptr(gaq), _ffi.ptr(gz), _ffi.ptr(gh), B, Ch, H * W,
+                                             _ffi.device_of(z), _ffi.stream_of(z))
         _ffi.check(rc, "dkt_gru_gate_out_bwd")
         return gaq if naq else None, gaq if ncq else None, gz, gh
 

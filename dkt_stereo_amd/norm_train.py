@@ -15,10 +15,6 @@ from torch.autograd.function import once_differentiable
 from . import _ffi
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _require_f32(*tensors):
     _ffi.require_gpu(*tensors)
     for t in tensors:
@@ -115,8 +111,8 @@ class _InstanceNormAddReluFn(torch.autograd.Function):
         ga = torch.empty_like(c) if need_a else None
         gc = torch.empty_like(c) if need_c else None
         ws = _bytes(L.dkt_instance_norm_bwd_workspace(planes, HW), c.device) if need_c else None
-        rc = L.dkt_instance_norm_add_relu_bwd(gout.data_ptr(), out.data_ptr(), c.data_ptr(), mi.data_ptr(), _ptr(ga), _ptr(gc),
-                                              _ptr(ws), planes, HW, _ffi.device_of(c), _ffi.stream_of(c))
+        rc = L.dkt_instance_norm_add_relu_bwd(gout.data_ptr(), out.data_ptr(), c.data_ptr(), mi.data_ptr(), _ffi.ptr(ga),
+                                              _ffi.ptr(gc), _ffi.ptr(ws), planes, HW, _ffi.device_of(c), _ffi.stream_of(c))
         _ffi.check(rc, "dkt_instance_norm_add_relu_bwd")
         return ga, gc, None
 

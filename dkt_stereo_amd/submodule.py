@@ -18,7 +18,7 @@ dkt_gwc_concat_volume_bwd (volumes_bwd.hip).  Otherwise nothing changes: the pla
 import torch
 
 from . import _ffi
-from .upsample import _aligned16, _batch_strided
+from . import upsample as _upsample
 
 
 def _check_pair(ref, tgt):
@@ -116,10 +116,6 @@ def _empty_or_none(need, like):
     return torch.empty_like(like) if need else None
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 class _GwcFn(torch.autograd.Function):
     """build_gwc_volume; backward dkt_gwc_volume_bwd."""
 
@@ -139,7 +135,7 @@ class _GwcFn(torch.autograd.Function):
         gt = _empty_or_none(ctx.needs_input_grad[1], tgt)
         if gr is None and gt is None:
             return None, None, None, None
-        rc = _ffi.lib().dkt_gwc_volume_bwd(gv.data_ptr(), bstride, ref.data_ptr(), tgt.data_ptr(), _ptr(gr), _ptr(gt),
+        rc = _ffi.lib().dkt_gwc_volume_bwd(gv.data_ptr(), bstride, ref.data_ptr(), tgt.data_ptr(), _ffi.ptr(gr), _ffi.ptr(gt),
                                            B, C, H, W, D, G, _ffi.device_of(ref), _ffi.stream_of(ref))
         _ffi.check(rc, "dkt_gwc_volume_bwd")
         return gr, gt, None, None
@@ -163,7 +159,7 @@ class _ConcatFn(torch.autograd.Function):
         gr, gt = mk(ctx.needs_input_grad[0]), mk(ctx.needs_input_grad[1])
         if gr is None and gt is None:
             return None, None, None, None
-        rc = _ffi.lib().dkt_concat_volume_bwd(gv.data_ptr(), bstride, _ptr(gr), _ptr(gt), B, C, H, W, D, int(ref_masked),
+        rc = _ffi.lib().dkt_concat_volume_bwd(gv.data_ptr(), bstride, _ffi.ptr(gr), _ffi.ptr(gt), B, C, H, W, D, int(ref_masked),
                                               _ffi.device_of(gv), _ffi.stream_of(gv))
         _ffi.check(rc, "dkt_concat_volume_bwd")
         return gr, gt, None, None
@@ -193,8 +189,8 @@ class _GwcConcatFn(torch.autograd.Function):
         cr, ct = mk(need[2]), mk(need[3])
         if gr is None and gt is None and cr is None and ct is None:
             return None, None, None, None, None, None
-        rc = _ffi.lib().dkt_gwc_concat_volume_bwd(gv.data_ptr(), bstride, gref.data_ptr(), gtgt.data_ptr(), _ptr(gr), _ptr(gt),
-                                                  B, C, G, _ptr(cr), _ptr(ct), Cc, 1, H, W, D,
+        rc = _ffi.lib().dkt_gwc_concat_volume_bwd(gv.data_ptr(), bstride, gref.data_ptr(), gtgt.data_ptr(), _ffi.ptr(gr), _ffi.ptr(gt),
+                                                  B, C, G, _ffi.ptr(cr), _ffi.ptr(ct), Cc, 1, H, W, D,
                                                   _ffi.device_of(gv), _ffi.stream_of(gv))
         _ffi.check(rc, "dkt_gwc_concat_volume_bwd")
         return gr, gt, cr, ct, None, None
@@ -262,48 +258,10 @@ def build_norm_correlation_volume(refimg_fea, targetimg_fea, maxdisp):
     return build_gwc_volume_norm(refimg_fea, targetimg_fea, maxdisp, 1)
 
 
-def _context_upsample(disp_low, up_weights):
-    """dkt_context_upsample on fp32 contiguous tensors."""
-    b, _, h, w = disp_low.shape
-    out = torch.empty((b, 4 * h, 4 * w), device=disp_low.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_context_upsample(disp_low.data_ptr(), up_weights.data_ptr(), out.data_ptr(), b, h, w,
-                                         _ffi.device_of(out), _ffi.stream_of(out))
-    _ffi.check(rc, "dkt_context_upsample")
-    return out
-
-
-class _ContextUpsampleFn(torch.autograd.Function):
-    """context_upsample under autograd: the forward is the inference kernel, the backward dkt_context_upsample_bwd
-    (context_upsample_train.hip), deterministic."""
-
-    @staticmethod
-    def forward(ctx, disp_low, up_weights):
-        ctx.save_for_backward(disp_low, up_weights)
-        return _context_upsample(disp_low, up_weights)
-
-    @staticmethod
-    def backward(ctx, gout):
-        disp_low, up_weights = ctx.saved_tensors
-        need_disp, need_weights = ctx.needs_input_grad
-        if not (need_disp or need_weights):
-            return None, None
-        _ffi.require_gpu(gout)
-        b, _, h, w = disp_low.shape
-        g, bstride = _batch_strided(gout.float().unsqueeze(1))
-        up_weights = _aligned16(up_weights)
-        gdisp = _empty_or_none(need_disp, disp_low)
-        gweights = _empty_or_none(need_weights, up_weights)
-        ws = torch.empty((b, 9, h, w), device=disp_low.device, dtype=torch.float32) if need_disp else None
-        rc = _ffi.lib().dkt_context_upsample_bwd(g.data_ptr(), bstride, disp_low.data_ptr(), up_weights.data_ptr(), _ptr(gdisp),
-                                                 _ptr(gweights), _ptr(ws), b, h, w, _ffi.device_of(g), _ffi.stream_of(g))
-        _ffi.check(rc, "dkt_context_upsample_bwd")
-        return gdisp, gweights
-
-
 def context_upsample(disp_low, up_weights):
     """meta_arch/igev_stereo/submodule.py:242-254: (B,1,h,w), (B,9,4h,4w) -> (B,4h,4w).  With grad enabled and an input that
-    requires grad the same kernel runs inside _ContextUpsampleFn (the same bits, HIP backward); non-fp32 inputs are cast
-    with .float() and autograd casts their gradients back."""
+    requires grad the same kernel runs inside upsample._ContextUpsampleFn (the same bits, HIP backward); non-fp32 inputs
+    are cast with .float() and autograd casts their gradients back."""
     disp_low, up_weights = disp_low.float(), up_weights.float()
     _ffi.require_gpu(disp_low, up_weights)
     b, c, h, w = disp_low.shape
@@ -311,9 +269,7 @@ def context_upsample(disp_low, up_weights):
         raise ValueError("context_upsample: disp_low %s / up_weights %s" % (tuple(disp_low.shape), tuple(up_weights.shape)))
     disp_low = disp_low.contiguous()
     up_weights = up_weights.contiguous()
-    if _needs_autograd(disp_low, up_weights):
-        return _ContextUpsampleFn.apply(disp_low, up_weights)
-    return _context_upsample(disp_low, up_weights)
+    return _upsample.context_upsample_weights(disp_low, up_weights, _needs_autograd(disp_low, up_weights))
 
 
 def disparity_regression(x, maxdisp):

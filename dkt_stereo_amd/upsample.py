@@ -3,8 +3,11 @@
 Forward: dkt_convex_upsample_fwd, the leading `channels` channels, bit-identical to the inference kernel's.  Backward:
 dkt_convex_upsample_bwd, deterministic, the softmax recomputed from the mask (only flow and mask are saved).
 
-IGEV's context up-sampling from logits (IGEVStereo.upsample_disp, igev_stereo.py:145-147) as one node:
-context_upsample_logits on dkt_context_upsample_logits_fwd / _bwd (context_upsample_train.hip)."""
+IGEV's context up-sampling (context_upsample_train.hip), the same operator on nine planes at full resolution, as two
+nodes: the weights form behind submodule.context_upsample (forward the inference kernel, backward
+dkt_context_upsample_bwd) and, from logits (IGEVStereo.upsample_disp, igev_stereo.py:145-147), context_upsample_logits on
+dkt_context_upsample_logits_fwd / _bwd.  The three backwards are one call each through _backward; their kernels share
+the nine-tap core of csrc/ups9.h."""
 import torch
 
 from . import _ffi
@@ -18,6 +21,25 @@ def _batch_strided(g):
         return g, g.stride(0)
     g = g.contiguous()
     return g, C * H * W
+
+
+def _backward(name, gout, coarse, nine, needs, channels, dims, scale=()):
+    """The backward of the three nodes: entry `name`(gout, its batch stride, coarse, nine, *scale, gcoarse, gnine, ws, *dims,
+    device, stream) -> (gcoarse, gnine), each None unless `needs` asks for it.  `gout` (N, C, fH, fW) is read in place where
+    its layout allows; the workspace (N, channels, 9, H, W) exists only beside the gradient of `coarse` (N, D, H, W)."""
+    need_coarse, need_nine = needs[:2]
+    if not (need_coarse or need_nine):
+        return None, None
+    _ffi.require_gpu(gout)
+    N, _, H, W = coarse.shape
+    g, bstride = _batch_strided(gout)
+    gcoarse = torch.empty_like(coarse) if need_coarse else None
+    gnine = torch.empty_like(nine) if need_nine else None
+    ws = torch.empty((N, channels, 9, H, W), device=coarse.device, dtype=torch.float32) if need_coarse else None
+    rc = getattr(_ffi.lib(), name)(g.data_ptr(), bstride, coarse.data_ptr(), nine.data_ptr(), *scale, _ffi.ptr(gcoarse),
+                                   _ffi.ptr(gnine), _ffi.ptr(ws), *dims, _ffi.device_of(g), _ffi.stream_of(g))
+    _ffi.check(rc, name)
+    return gcoarse, gnine
 
 
 class _ConvexUpsampleFn(torch.autograd.Function):
@@ -39,21 +61,9 @@ class _ConvexUpsampleFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         flow, mask = ctx.saved_tensors
-        need_flow, need_mask = ctx.needs_input_grad[:2]
-        if not (need_flow or need_mask):
-            return None, None, None, None
-        _ffi.require_gpu(gout)
         N, D, H, W = flow.shape
-        gout, bstride = _batch_strided(gout)
-        gflow = torch.empty_like(flow) if need_flow else None
-        gmask = torch.empty_like(mask) if need_mask else None
-        ws = torch.empty((N, ctx.channels, 9, H, W), device=flow.device, dtype=torch.float32) if need_flow else None
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        rc = _ffi.lib().dkt_convex_upsample_bwd(gout.data_ptr(), bstride, flow.data_ptr(), mask.data_ptr(), ptr(gflow), ptr(gmask),
-                                                ptr(ws), N, D, ctx.channels, H, W, ctx.factor,
-                                                _ffi.device_of(flow), _ffi.stream_of(flow))
-        _ffi.check(rc, "dkt_convex_upsample_bwd")
-        return gflow, gmask, None, None
+        return _backward("dkt_convex_upsample_bwd", gout, flow, mask, ctx.needs_input_grad, ctx.channels,
+                         (N, D, ctx.channels, H, W, ctx.factor)) + (None, None)
 
 
 def convex_upsample(flow, mask, factor, channels=None):
@@ -69,6 +79,39 @@ def convex_upsample(flow, mask, factor, channels=None):
 def _aligned16(t):
     """`t` (contiguous) at a 16-byte aligned address: the nine-plane tensors are moved 16 bytes at a time."""
     return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _context_upsample(disp_low, up_weights):
+    """dkt_context_upsample on fp32 contiguous tensors."""
+    b, _, h, w = disp_low.shape
+    out = torch.empty((b, 4 * h, 4 * w), device=disp_low.device, dtype=torch.float32)
+    rc = _ffi.lib().dkt_context_upsample(disp_low.data_ptr(), up_weights.data_ptr(), out.data_ptr(), b, h, w,
+                                         _ffi.device_of(out), _ffi.stream_of(out))
+    _ffi.check(rc, "dkt_context_upsample")
+    return out
+
+
+class _ContextUpsampleFn(torch.autograd.Function):
+    """context_upsample under autograd: the forward is the inference kernel, the backward dkt_context_upsample_bwd
+    (context_upsample_train.hip), deterministic."""
+
+    @staticmethod
+    def forward(ctx, disp_low, up_weights):
+        ctx.save_for_backward(disp_low, up_weights)
+        return _context_upsample(disp_low, up_weights)
+
+    @staticmethod
+    def backward(ctx, gout):
+        disp_low, up_weights = ctx.saved_tensors
+        b, _, h, w = disp_low.shape
+        return _backward("dkt_context_upsample_bwd", gout.unsqueeze(1), disp_low, _aligned16(up_weights), ctx.needs_input_grad,
+                         1, (b, h, w))
+
+
+def context_upsample_weights(disp_low, up_weights, differentiable):
+    """The weights form on fp32 contiguous tensors (submodule.context_upsample prepares them and decides): (B, 1, h, w),
+    (B, 9, 4h, 4w) -> (B, 4h, 4w), the plain kernel call or, when `differentiable`, the same call inside _ContextUpsampleFn."""
+    return _ContextUpsampleFn.apply(disp_low, up_weights) if differentiable else _context_upsample(disp_low, up_weights)
 
 
 class _ContextUpsampleLogitsFn(torch.autograd.Function):
@@ -89,21 +132,9 @@ class _ContextUpsampleLogitsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         disp_low, logits = ctx.saved_tensors
-        need_disp, need_logits = ctx.needs_input_grad[:2]
-        if not (need_disp or need_logits):
-            return None, None, None
-        _ffi.require_gpu(gout)
         B, _, h, w = disp_low.shape
-        g, bstride = _batch_strided(gout.float().unsqueeze(1))
-        gdisp = torch.empty_like(disp_low) if need_disp else None
-        glogits = torch.empty_like(logits) if need_logits else None
-        ws = torch.empty((B, 9, h, w), device=disp_low.device, dtype=torch.float32) if need_disp else None
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        rc = _ffi.lib().dkt_context_upsample_logits_bwd(g.data_ptr(), bstride, disp_low.data_ptr(), logits.data_ptr(), ctx.scale,
-                                                        ptr(gdisp), ptr(glogits), ptr(ws), B, h, w,
-                                                        _ffi.device_of(g), _ffi.stream_of(g))
-        _ffi.check(rc, "dkt_context_upsample_logits_bwd")
-        return gdisp, glogits, None
+        return _backward("dkt_context_upsample_logits_bwd", gout.unsqueeze(1), disp_low, logits, ctx.needs_input_grad, 1,
+                         (B, h, w), scale=(ctx.scale,)) + (None,)
 
 
 def context_upsample_logits(disp_low, logits, scale=4.0):

@@ -172,6 +172,30 @@ def test_scale_must_be_a_power_of_two():
     context_upsample_logits(G(disp), G(lg), 0.5)
 
 
+@pytest.mark.parametrize("name", ["h1", "tiles", "sigma32"])
+def test_logits_form_is_the_convex_form_at_f4(name):
+    """context_upsample_logits(disp, logits, 4) is convex_upsample(disp, mask, 4, 1) on the planes re-laid-out as
+    mask[b, (k*4 + i)*4 + j, y, x] = logits[b, k, 4y + i, 4x + j]: the nine-tap core of ups9.h runs the same operation
+    sequence per element in both (softmax, fl(4 nb), sum_k fl(p_k v_k) from 0 in ascending k; a_k, s, fl(p_k fl(a_k - s));
+    C in ascending j, then i; the gather in ascending k, times the factor), so out, the coarse gradient and the nine-plane
+    gradient are equal, the wide case (the softmax's rare division path) included.  torch.equal, not R.same: the convex
+    kernel adds +0 where the logits kernel does not (its masked second channel, its accumulators starting at 0), which
+    can change the sign of a zero and nothing else."""
+    from dkt_stereo_amd.upsample import context_upsample_logits, convex_upsample
+    disp, logits, gout = (G(x) for x in _ref(name, True)[0])
+    B, _, h, w = disp.shape
+    mask = logits.view(B, 9, h, 4, w, 4).permute(0, 1, 3, 5, 2, 4).reshape(B, 144, h, w)
+    a, b = disp.clone().requires_grad_(True), mask.clone().requires_grad_(True)
+    cv = convex_upsample(a, b, 4, 1)
+    cv.backward(gout[:, None])
+    c, d = disp.clone().requires_grad_(True), logits.clone().requires_grad_(True)
+    lg = context_upsample_logits(c, d, 4.0)
+    lg.backward(gout)
+    assert torch.equal(cv.detach()[:, 0], lg.detach()), name
+    assert torch.equal(a.grad, c.grad), name
+    assert torch.equal(b.grad.view(B, 9, 4, 4, h, w).permute(0, 1, 4, 2, 5, 3).reshape(B, 9, 4 * h, 4 * w), d.grad), name
+
+
 def test_logits_form_is_the_weights_form_behind_a_softmax():
     """context_upsample_logits(disp, logits, 4) and context_upsample(4 disp, softmax(logits)) on the device differ by the
     softmax's roundings only: both meet the out bound."""
