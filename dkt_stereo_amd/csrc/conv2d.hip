@@ -34,6 +34,7 @@
 // chunk c; one barrier per chunk.
 #include "dkt_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -137,6 +138,52 @@ __device__ __forceinline__ unsigned pack_h2(_Float16 a, _Float16 b) {
 
 struct ConvArgsPair {
     ConvArgs p[2];
+};
+
+// A wave-uniform value pinned to scalar registers: what comes out cannot be recomputed (or re-loaded from the argument
+// segment) from what went in.  (readfirstlane first: a uniform value the compiler computed on the vector ALU -- the
+// quotients of decode() -- is in a vector register.)  The epilogue reads its arguments through these, once per tile.
+__device__ __forceinline__ unsigned conv_hold(unsigned x) {
+    x = __builtin_amdgcn_readfirstlane(x);
+    asm volatile("" : "+s"(x));
+    return x;
+}
+__device__ __forceinline__ int conv_hold(int x) { return (int)conv_hold((unsigned)x); }
+__device__ __forceinline__ float conv_hold(float x) { return __uint_as_float(conv_hold(__float_as_uint(x))); }
+template <class T>
+__device__ __forceinline__ T *conv_hold(T *p) {
+    // (every pointer of the argument structure is a global one; rebuilt from two integers it would be a flat one)
+    const unsigned long long v = (unsigned long long)p;
+    return (T *)(__attribute__((address_space(1))) T *)(((unsigned long long)conv_hold((unsigned)(v >> 32)) << 32) | conv_hold((unsigned)v));
+}
+// Four pointers in ONE statement: the scalar loads they are formed from are issued back to back behind one wait (a
+// statement per pointer is a load, a wait and the statement, pointer after pointer).
+template <class T0, class T1, class T2, class T3>
+__device__ __forceinline__ void conv_hold4(T0 *&p0, T1 *&p1, T2 *&p2, T3 *&p3) {
+    const unsigned long long v0 = (unsigned long long)p0, v1 = (unsigned long long)p1, v2 = (unsigned long long)p2, v3 = (unsigned long long)p3;
+    unsigned l0 = __builtin_amdgcn_readfirstlane((unsigned)v0), h0 = __builtin_amdgcn_readfirstlane((unsigned)(v0 >> 32));
+    unsigned l1 = __builtin_amdgcn_readfirstlane((unsigned)v1), h1 = __builtin_amdgcn_readfirstlane((unsigned)(v1 >> 32));
+    unsigned l2 = __builtin_amdgcn_readfirstlane((unsigned)v2), h2 = __builtin_amdgcn_readfirstlane((unsigned)(v2 >> 32));
+    unsigned l3 = __builtin_amdgcn_readfirstlane((unsigned)v3), h3 = __builtin_amdgcn_readfirstlane((unsigned)(v3 >> 32));
+    asm volatile("" : "+s"(l0), "+s"(h0), "+s"(l1), "+s"(h1), "+s"(l2), "+s"(h2), "+s"(l3), "+s"(h3));
+    p0 = (T0 *)(__attribute__((address_space(1))) T0 *)(((unsigned long long)h0 << 32) | l0);
+    p1 = (T1 *)(__attribute__((address_space(1))) T1 *)(((unsigned long long)h1 << 32) | l1);
+    p2 = (T2 *)(__attribute__((address_space(1))) T2 *)(((unsigned long long)h2 << 32) | l2);
+    p3 = (T3 *)(__attribute__((address_space(1))) T3 *)(((unsigned long long)h3 << 32) | l3);
+}
+// The same for an address formed per access, without `volatile` (a volatile statement is a fence for the memory operations
+// around it: the loads of an operand batch would go out one by one); this one only cannot be folded into the lane offset
+// that is added to it, so the access keeps the form scalar base + 32-bit lane offset.
+template <class T>
+__device__ __forceinline__ T *conv_base(T *p) {
+    unsigned long long v = (unsigned long long)p;
+    unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    asm("" : "+s"(lo), "+s"(hi));
+    return (T *)(__attribute__((address_space(1))) T *)(((unsigned long long)hi << 32) | lo);
+}
+template <int V>
+struct ConvTag {
+    static constexpr int value = V;
 };
 
 // DSC = 1: in_scale / out_scale come from device memory -- the input gradient of a convolution, whose
@@ -379,21 +426,54 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
     // second half); a sched_group_barrier pattern asks for ~1 memory op + 3 VALU per MFMA.
     // Idle waves (co >= CoutPad) run the same stream on clamped weights and store nothing:
     // a wave-uniform branch here would split the scheduling region.
-    auto epilogue = [&]() {
+    // ARGUMENTS: `a` lives in the kernel-argument segment, so every `a.field` is a scalar load, and with the scalar registers
+    // this kernel has left the compiler re-issued that load (and drained lgkmcnt for it) at each use: once per stored value.
+    // Behind the tile's last MFMA nothing of this wave hides those round trips, so the epilogue reads what it needs ONCE per
+    // tile into locals that conv_hold() makes opaque, decides the wave-uniform switches once (one dispatch to bodies
+    // specialised at compile time: kind, z or r half, statistics, FAST) and addresses every tensor as wave-uniform base + one
+    // lane offset per row.  FAST = the wave's 32 MF channels all exist (no channel guard) and its 32 MF planes span less than
+    // 2^31 bytes (the lane offset fits 32 bits: scalar base + 32-bit vector offset, the base of each value advanced on the
+    // scalar ALU); every other tile keeps the per-value guard and 64-bit lane offsets.
+    auto epilogue = [&]() __attribute__((always_inline)) {
         // ---- epilogue: un-scale, bias, optional ReLU, NCHW stores (128-byte rows) ----
-        const int co_w = co_blk + wm * 32 * MF;            // this wave's first output channel
-        if (co_w >= a.CoutPad) return;                     // idle wave
+        const int co_w = conv_hold(co_blk + wm * 32 * MF);         // this wave's first output channel
+        // (ONE statement holds the batch: its scalar loads are issued back to back behind one wait; a statement per field
+        // would be a load, a wait and the statement, field after field)
+        auto sgpr = [](auto x) { return __builtin_amdgcn_readfirstlane((unsigned)x); };    // (a no-op on what is scalar already)
+        unsigned epi_u = sgpr(a.epi), Cout_u = sgpr(a.Cout), relu_f = sgpr(a.relu), oh_ = sgpr(a.Ho), ow_ = sgpr(a.Wo), ih_ = sgpr(a.H), iw_ = sgpr(a.W);
+        unsigned want_stats = sgpr(!DSC && a.stats_ws != nullptr ? 1 : 0), CoutPad_u = sgpr(a.CoutPad);
+        unsigned osc_u = sgpr(__float_as_uint(DSC ? dsc_out : a.out_scale));
+        unsigned bias_lo = sgpr((unsigned long long)a.bias), bias_hi = sgpr((unsigned long long)a.bias >> 32);
+        asm volatile("" : "+s"(epi_u), "+s"(Cout_u), "+s"(relu_f), "+s"(oh_), "+s"(ow_), "+s"(ih_), "+s"(iw_), "+s"(want_stats),
+                          "+s"(CoutPad_u), "+s"(osc_u), "+s"(bias_lo), "+s"(bias_hi));
+        const float osc = __uint_as_float(osc_u);
+        const int epi = (int)epi_u, Cout = (int)Cout_u;
+        if (co_w >= (int)CoutPad_u) return;                        // idle wave
+        const float *const bias_p = (const float *)(__attribute__((address_space(1))) const float *)(((unsigned long long)bias_hi << 32) | bias_lo);
+        // the plane of the epilogue's tensors: the output's (kind 0; == H x W at stride 1), H x W for the gate kinds
+        const int PH = (int)(epi == 0 ? oh_ : ih_), PW = (int)(epi == 0 ? ow_ : iw_);
+        const int plane = conv_hold(PH * PW);
+        const int bi = conv_hold(b), row0 = conv_hold(h0 + wn * NF);
+        const int ow = w0 + li;
+        const bool relu = relu_f != 0;
         // this lane's 32 output channels: co = co_lane + m*32 + (r&3) + 8*(r>>2); their biases
         // are fetched as one batch of independent loads (clamped index, no per-element branch)
         const int co_lane = co_w + 4 * kg;
         float bv[MF][16];
+        if (bias_p) {
 #pragma unroll
-        for (int m = 0; m < MF; ++m)
+            for (int m = 0; m < MF; ++m)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co_lane + m * 32 + (r & 3) + 8 * (r >> 2);
-                bv[m][r] = a.bias ? a.bias[co < a.Cout ? co : a.Cout - 1] : 0.0f;
-            }
+                for (int r = 0; r < 16; ++r) {
+                    const int co = co_lane + m * 32 + (r & 3) + 8 * (r >> 2);
+                    bv[m][r] = bias_p[co < Cout ? co : Cout - 1];
+                }
+        } else {
+#pragma unroll
+            for (int m = 0; m < MF; ++m)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) bv[m][r] = 0.0f;
+        }
         // The biases land HERE, once, and reach the stores below as values no load is pending on.  Left to the compiler, every
         // use of a bias behind a guarded store got a drained wait of its own (it cannot count the stores a masked block issued):
         // in the plain epilogue each of a row's 16 MF stores was waited on before the next one was issued.
@@ -402,131 +482,193 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
         for (int m = 0; m < MF; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bv[m][r]));
-        const bool all_co = co_w + 32 * MF <= a.Cout;            // wave-uniform: no channel guard needed
-        const int iHW = (int)HW;
-        if (a.epi == 0) {
-            const int oHW = a.Ho * a.Wo;                    // output plane (== HW when ST == 1)
-            float *ob = a.out + (long)b * a.out_bs + (long)co_lane * oHW;
+        const bool all_co = co_w + 32 * MF <= Cout;              // wave-uniform: no channel guard needed
+        const bool fast = all_co && (long)plane * (32 * MF * 4) < (1L << 31);
+        // the value (m, n, r) of this lane: un-scaled, biased, ReLU as a select on the held flag.  The statistics recompute
+        // their values from the accumulators with a scale of their own (the same number, opaque): were the two passes to share
+        // the values, 16 MF NF of them would be kept beside the accumulators across the row masks (measured: the 1x1 forms went
+        // from 159 to 233 registers, three blocks per CU to two).
+        auto value = [&](int m, int n, int r, float scale) {
+            const float v = acc[m][n][r] * scale + bv[m][r];
+            return (relu && v < 0.0f) ? 0.0f : v;
+        };
+        // address of channel dco (relative to the wave's first) of a tensor whose plane of the wave's first channel is p;
+        // the lane adds loff bytes: its channel half, row and column
+        auto at = [&](auto kFast, const float *p, int dco, auto loff) __attribute__((always_inline)) -> float * {
+            return (float *)(conv_base((const char *)p + (long)dco * plane * 4) + loff);
+        };
+        // ---- kind 0: plain stores
+        auto body_plain = [&](auto kFast) __attribute__((always_inline)) {
+            constexpr bool FAST = decltype(kFast)::value != 0;
+            using OT = std::conditional_t<FAST, unsigned, long>;
+            float *const ob = conv_hold(a.out + (long)bi * a.out_bs + (long)co_w * plane);
+            const OT kgo = (OT)(4 * kg) * (OT)plane;
 #pragma unroll
             for (int n = 0; n < NF; ++n) {
-                const int oh = h0 + wn * NF + n, ow = w0 + li;
-                if (oh >= a.Ho || ow >= a.Wo) continue;
-                float *op = ob + (long)oh * a.Wo + ow;
+                const int oh = row0 + n;
+                if (oh >= PH || ow >= PW) continue;
+                const OT loff = (kgo + (OT)oh * (OT)PW + (OT)ow) * 4;
 #pragma unroll
                 for (int m = 0; m < MF; ++m)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int dco = m * 32 + (r & 3) + 8 * (r >> 2);
-                        float v = acc[m][n][r] * (DSC ? dsc_out : a.out_scale) + bv[m][r];
-                        if (a.relu) v = dkt_relu(v);
-                        if (all_co || co_lane + dco < a.Cout) op[dco * oHW] = v;
+                        const float v = value(m, n, r, osc);
+                        if (FAST || co_lane + dco < Cout) *at(kFast, ob, dco, loff) = v;
+                        if (!FAST && (r & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // (no row's worth of 64-bit addresses formed ahead)
                     }
             }
-            if (a.stats_ws) {
-                // sums / sums of squares of the values just stored: per lane over its NF pixels, then a reduce-scatter over the
-                // 32 pixel lanes of the half-wave (31 exchanges per statistic instead of 160): lane li ends with value index li.
-                // Channel blocks go in groups of two (32 values per lane) and, for an odd MF, a last single one (16 values: the
-                // first exchange only adds, lane li & 15 ends with value li & 15).
-                auto stats_group = [&](const int m0, const int nm) {
-                    float s1[32], s2[32];
+        };
+        // ---- kind 0: the statistics of the values just stored
+        auto body_stats = [&]() __attribute__((always_inline)) {
+            const float osc_s = conv_hold(osc);
+            const long e = (long)((h0 / (NF * WN)) * a.tiles_w + w0 / 32) * WN + wn;
+            // (the statistics rows of this wave's first channel; a lane adds the channel it ends up holding)
+            float *const sws = conv_hold(a.stats_ws + (((long)bi * a.tiles_xy * WN + e) * Cout + co_w) * 2);
+            // sums / sums of squares of the values just stored: per lane over its NF pixels, then a reduce-scatter over the
+            // 32 pixel lanes of the half-wave (31 exchanges per statistic instead of 160): lane li ends with value index li.
+            // Channel blocks go in groups of two (32 values per lane) and, for an odd MF, a last single one (16 values: the
+            // first exchange only adds, lane li & 15 ends with value li & 15).
+            auto stats_group = [&](const int m0, const int nm) {
+                float s1[32], s2[32];
 #pragma unroll
-                    for (int i = 0; i < 32; ++i) s1[i] = s2[i] = 0.0f;
+                for (int i = 0; i < 32; ++i) s1[i] = s2[i] = 0.0f;
 #pragma unroll
-                    for (int n = 0; n < NF; ++n) {
-                        const int oh = h0 + wn * NF + n, ow = w0 + li;
-                        const bool ok = oh < a.Ho && ow < a.Wo;
+                for (int n = 0; n < NF; ++n) {
+                    const bool ok = row0 + n < PH && ow < PW;
 #pragma unroll
-                        for (int mm = 0; mm < nm; ++mm)
+                    for (int mm = 0; mm < nm; ++mm)
 #pragma unroll
-                            for (int r = 0; r < 16; ++r) {
-                                float v = acc[m0 + mm][n][r] * (DSC ? dsc_out : a.out_scale) + bv[m0 + mm][r];
-                                if (a.relu) v = dkt_relu(v);
-                                v = ok ? v : 0.0f;
-                                s1[mm * 16 + r] = __fadd_rn(s1[mm * 16 + r], v);
-                                s2[mm * 16 + r] = __fadd_rn(s2[mm * 16 + r], __fmul_rn(v, v));
-                            }
+                        for (int r = 0; r < 16; ++r) {
+                            const float v = ok ? value(m0 + mm, n, r, osc_s) : 0.0f;
+                            s1[mm * 16 + r] = __fadd_rn(s1[mm * 16 + r], v);
+                            s2[mm * 16 + r] = __fadd_rn(s2[mm * 16 + r], __fmul_rn(v, v));
+                        }
+                }
+                if (nm == 1) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        s1[i] = __fadd_rn(s1[i], __shfl_xor(s1[i], 16, 32));
+                        s2[i] = __fadd_rn(s2[i], __shfl_xor(s2[i], 16, 32));
                     }
-                    if (nm == 1) {
+                }
 #pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            s1[i] = __fadd_rn(s1[i], __shfl_xor(s1[i], 16, 32));
-                            s2[i] = __fadd_rn(s2[i], __shfl_xor(s2[i], 16, 32));
+                for (int d = 16; d >= 1; d >>= 1) {
+                    if (nm == 1 && d == 16) continue;
+                    const bool up = (li & d) != 0;
+#pragma unroll
+                    for (int j = 0; j < d; ++j) {
+                        const float k1 = up ? s1[j + d] : s1[j], g1 = up ? s1[j] : s1[j + d];
+                        const float k2 = up ? s2[j + d] : s2[j], g2 = up ? s2[j] : s2[j + d];
+                        s1[j] = __fadd_rn(k1, __shfl_xor(g1, d, 32));
+                        s2[j] = __fadd_rn(k2, __shfl_xor(g2, d, 32));
+                    }
+                }
+                const int vi = nm == 1 ? (li & 15) : li;                 // value index this lane holds
+                const int dco = (m0 + (vi >> 4)) * 32 + (vi & 3) + 8 * ((vi & 15) >> 2);
+                const int co = co_lane + dco;
+                if (co < Cout && (nm == 2 || li < 16)) {
+                    float *p = sws + (4 * kg + dco) * 2;
+                    p[0] = s1[0];
+                    p[1] = s2[0];
+                }
+            };
+#pragma unroll
+            for (int m0 = 0; m0 + 1 < MF; m0 += 2) stats_group(m0, 2);
+            if (MF & 1) stats_group(MF - 1, 1);
+        };
+        // ---- fused GRU gates (gru_gates.hip arithmetic with hardware exp/rcp) ----
+        // EPI: kind 1 (merged z|r), 2 (q), 3 (residual join); RPART (kind 1): this wave owns r channels
+        auto body_gate = [&](auto kEpi, auto kRpart, auto kFast) __attribute__((always_inline)) {
+            constexpr int EPI = decltype(kEpi)::value;
+            constexpr bool RPART = decltype(kRpart)::value != 0, FAST = decltype(kFast)::value != 0;
+            constexpr bool LOAD_H = EPI == 2 || RPART, LOAD_Z = EPI == 2;
+            using OT = std::conditional_t<FAST, unsigned, long>;
+            const int Ch = EPI == 1 ? Cout / 2 : Cout;
+            const long cb = (long)(co_w - (RPART ? Ch : 0)) * plane;      // the wave's first channel inside the Ch-wide gate tensors
+            const float *pc = (RPART ? a.e_c1 + (long)bi * a.e_c1_bs : a.e_c0 + (long)bi * a.e_c0_bs) + cb;
+            const float *pz = LOAD_Z ? a.e_c1 + (long)bi * a.e_c1_bs + cb : pc;
+            const float *ph = LOAD_H ? a.e_h + (long)bi * a.e_h_bs + cb : pc;
+            float *po = (RPART ? a.out2 + (long)bi * a.out2_bs : a.out + (long)bi * a.out_bs) + cb;
+            conv_hold4(pc, pz, ph, po);
+            const OT kgo = (OT)(4 * kg) * (OT)plane;
+#pragma unroll
+            for (int n = 0; n < NF; ++n) {
+                const int oh = row0 + n;
+                if (oh >= PH || ow >= PW) continue;
+                const OT loff = (kgo + (OT)oh * (OT)PW + (OT)ow) * 4;
+#pragma unroll
+                for (int mh = 0; mh < 2 * MF; ++mh) {
+                    // the gate operands of 8 channels are fetched as one batch BEFORE any store (hout
+                    // may alias h, so the compiler cannot hoist the loads over stores itself); batches
+                    // of 8 rather than 16 keep the kernel inside the 256-VGPR budget of two blocks/CU
+                    const int m = mh >> 1, r0 = (mh & 1) * 8;
+                    float gc[8], gh[8], gz[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int r = r0 + i;
+                        const int dco = m * 32 + (r & 3) + 8 * (r >> 2);
+                        if constexpr (FAST) {
+                            gc[i] = *at(kFast, pc, dco, loff);
+                            gh[i] = LOAD_H ? *at(kFast, ph, dco, loff) : 0.0f;
+                            gz[i] = LOAD_Z ? *at(kFast, pz, dco, loff) : 0.0f;
+                        } else {
+                            // (a channel past the last one reads the lane's first channel: a valid address, the value unused)
+                            const long o = (co_lane + dco < Cout ? (long)conv_base((const char *)nullptr + (long)dco * plane * 4) : 0L) + loff;
+                            gc[i] = *(const float *)((const char *)pc + o);
+                            gh[i] = LOAD_H ? *(const float *)((const char *)ph + o) : 0.0f;
+                            gz[i] = LOAD_Z ? *(const float *)((const char *)pz + o) : 0.0f;
                         }
                     }
 #pragma unroll
-                    for (int d = 16; d >= 1; d >>= 1) {
-                        if (nm == 1 && d == 16) continue;
-                        const bool up = (li & d) != 0;
-#pragma unroll
-                        for (int j = 0; j < d; ++j) {
-                            const float k1 = up ? s1[j + d] : s1[j], g1 = up ? s1[j] : s1[j + d];
-                            const float k2 = up ? s2[j + d] : s2[j], g2 = up ? s2[j] : s2[j + d];
-                            s1[j] = __fadd_rn(k1, __shfl_xor(g1, d, 32));
-                            s2[j] = __fadd_rn(k2, __shfl_xor(g2, d, 32));
+                    for (int i = 0; i < 8; ++i) {
+                        const int r = r0 + i;
+                        const int dco = m * 32 + (r & 3) + 8 * (r >> 2);
+                        if (!(FAST || co_lane + dco < Cout)) continue;
+                        float *const o = at(kFast, po, dco, loff);
+                        const float v = acc[m][n][r] * osc + bv[m][r];
+                        if constexpr (EPI == 1) {
+                            const float g = conv_sigmoid(__fadd_rn(v, gc[i]));
+                            *o = RPART ? __fmul_rn(g, gh[i]) : g;
+                        } else if constexpr (EPI == 3) {
+                            *o = dkt_relu(__fadd_rn(gc[i], (relu && v < 0.0f) ? 0.0f : v));
+                        } else {
+                            const float q = conv_tanh(__fadd_rn(v, gc[i]));
+                            *o = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, gz[i]), gh[i]), __fmul_rn(gz[i], q));
                         }
                     }
-                    const int vi = nm == 1 ? (li & 15) : li;                 // value index this lane holds
-                    const int dco = (m0 + (vi >> 4)) * 32 + (vi & 3) + 8 * ((vi & 15) >> 2);
-                    const int co = co_lane + dco;
-                    const long e = (long)((h0 / (NF * WN)) * a.tiles_w + w0 / 32) * WN + wn;
-                    if (co < a.Cout && (nm == 2 || li < 16)) {
-                        float *p = a.stats_ws + (((long)b * a.tiles_xy * WN + e) * a.Cout + co) * 2;
-                        p[0] = s1[0];
-                        p[1] = s2[0];
-                    }
-                };
-#pragma unroll
-                for (int m0 = 0; m0 + 1 < MF; m0 += 2) stats_group(m0, 2);
-                if (MF & 1) stats_group(MF - 1, 1);
+                    __builtin_amdgcn_sched_barrier(0);           // one operand batch at a time (see above: the register budget)
+                }
+            }
+        };
+        // ---- one dispatch per tile.  What no host path launches is not instantiated: the gate kinds need stride 1 and host
+        // scales (conv_fill refuses them at stride 2, the device-scaled entry has none), kinds 1 and 2 no input norm
+        // (conv_fill_desc), and the device-scaled entry asks for no statistics.
+        if (epi == 0) {
+            const bool stats = want_stats != 0;
+            if (fast) body_plain(ConvTag<1>{});
+            else body_plain(ConvTag<0>{});
+            if constexpr (!DSC) {
+                if (stats) body_stats();
             }
             return;
         }
-        // ---- fused GRU gates (gru_gates.hip arithmetic with hardware exp/rcp) ----
-        const int Ch = a.epi == 1 ? a.Cout / 2 : a.Cout;
-        const bool second = a.epi == 1 && co_w >= Ch;       // wave-uniform: this wave owns r channels
-        const int cg = co_lane - (second ? Ch : 0);         // channel inside the Ch-wide gate tensors
-        const float *pc = (second ? a.e_c1 : a.e_c0) + (long)b * (second ? a.e_c1_bs : a.e_c0_bs) + (long)cg * HW;
-        const float *pz = a.e_c1 + (long)b * a.e_c1_bs + (long)cg * HW;       // epi 2 only
-        const float *ph = a.e_h + (long)b * a.e_h_bs + (long)cg * HW;
-        float *po = (second ? a.out2 + (long)b * a.out2_bs : a.out + (long)b * a.out_bs) + (long)cg * HW;
-#pragma unroll
-        for (int n = 0; n < NF; ++n) {
-            const int oh = h0 + wn * NF + n, ow = w0 + li;
-            if (oh >= a.H || ow >= a.W) continue;
-            const long px = (long)oh * a.W + ow;
-#pragma unroll
-            for (int mh = 0; mh < 2 * MF; ++mh) {
-                // the gate operands of 8 channels are fetched as one batch BEFORE any store (hout
-                // may alias h, so the compiler cannot hoist the loads over stores itself); batches
-                // of 8 rather than 16 keep the kernel inside the 256-VGPR budget of two blocks/CU
-                const int m = mh >> 1, r0 = (mh & 1) * 8;
-                float gc[8], gh[8], gz[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int r = r0 + i;
-                    const int dco = m * 32 + (r & 3) + 8 * (r >> 2);
-                    const bool ok = all_co || co_lane + dco < a.Cout;
-                    const long o = (long)(ok ? dco : 0) * iHW + px;
-                    gc[i] = pc[o];
-                    gh[i] = (a.epi == 2 || second) ? ph[o] : 0.0f;
-                    gz[i] = a.epi == 2 ? pz[o] : 0.0f;
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int r = r0 + i;
-                    const int dco = m * 32 + (r & 3) + 8 * (r >> 2);
-                    if (!(all_co || co_lane + dco < a.Cout)) continue;
-                    const long o = (long)dco * iHW + px;
-                    const float v = acc[m][n][r] * (DSC ? dsc_out : a.out_scale) + bv[m][r];
-                    if (a.epi == 1) {
-                        const float g = conv_sigmoid(__fadd_rn(v, gc[i]));
-                        po[o] = second ? __fmul_rn(g, gh[i]) : g;
-                    } else if (a.epi == 3) {
-                        po[o] = dkt_relu(__fadd_rn(gc[i], a.relu ? dkt_relu(v) : v));
-                    } else {
-                        const float q = conv_tanh(__fadd_rn(v, gc[i]));
-                        po[o] = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, gz[i]), gh[i]), __fmul_rn(gz[i], q));
-                    }
+        if constexpr (ST == 1 && !DSC) {
+            if (epi == 3) {
+                if (fast) body_gate(ConvTag<3>{}, ConvTag<0>{}, ConvTag<1>{});
+                else body_gate(ConvTag<3>{}, ConvTag<0>{}, ConvTag<0>{});
+                return;
+            }
+            if constexpr (!NRM) {
+                if (epi == 2) {
+                    if (fast) body_gate(ConvTag<2>{}, ConvTag<0>{}, ConvTag<1>{});
+                    else body_gate(ConvTag<2>{}, ConvTag<0>{}, ConvTag<0>{});
+                } else if (co_w >= Cout / 2) {                  // kind 1, the r half
+                    if (fast) body_gate(ConvTag<1>{}, ConvTag<1>{}, ConvTag<1>{});
+                    else body_gate(ConvTag<1>{}, ConvTag<1>{}, ConvTag<0>{});
+                } else {
+                    if (fast) body_gate(ConvTag<1>{}, ConvTag<0>{}, ConvTag<1>{});
+                    else body_gate(ConvTag<1>{}, ConvTag<0>{}, ConvTag<0>{});
                 }
             }
         }
