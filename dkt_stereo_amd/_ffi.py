@@ -168,6 +168,7 @@ SIGNATURES = {
     "dkt_conv2d_c8_pair": [ctypes.POINTER(ConvC8Desc), ctypes.POINTER(ConvC8Desc), _i, _i, _vp],
     "dkt_conv2d_f16s_pair": [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), _i, _i, _vp],
     "dkt_conv2d_f16s_desc": [ctypes.POINTER(ConvDesc), _i, _i, _vp],
+    "dkt_conv2d_f16s_tile": [_i, _i, _i, _i, _ip, _i, _i, _i, _i, _i, _i, _ip],
     "dkt_corr1d_build": [_vp, _vp, _pp, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
     "dkt_corr1d_lookup": [_pp, _vp, _l, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_convex_upsample": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],

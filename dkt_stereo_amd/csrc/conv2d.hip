@@ -31,9 +31,12 @@
 // channels (MF = 2; 1 for the 1-2 channel heads) x NF rows x 32 columns; WM x WN waves along (channels, rows).  Blocks are
 // persistent (a stream of tiles per block); LDS is double buffered: the fp32 loads of
 // chunk c+1 -- of this tile or the block's next one -- are in flight under the MFMAs of
-// chunk c; one barrier per chunk.
+// chunk c; one barrier per chunk.  Which instantiation a call runs on -- the tile shape by layer width and image size, the
+// stride-2 shapes, the weights-stationary kernel of conv_ws.h -- is decided in conv_tile.h and nowhere else.
 #include "dkt_common.h"
+#include "conv_tile.h"
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -46,9 +49,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #endif
 #ifndef CONV_MIN_BLOCKS
 #define CONV_MIN_BLOCKS 2    // blocks per CU the register budget is capped for (256 VGPRs)
-#endif
-#ifndef CONV_FEW_TILES
-#define CONV_FEW_TILES 200   // fewer tiles than this: half-height tile shapes
 #endif
 #ifndef CONV_AR_NF1
 #define CONV_AR_NF1 3
@@ -857,10 +857,9 @@ static int launch_conv(ConvArgs a, int B, hipStream_t st, const ConvSecond *sec 
     const long total = (long)a.tiles_xy * a.n_co * B;
     if (total > 0x7fffffffL) return DKT_E_SHAPE;
     a.total_tiles = (int)total;
-    constexpr bool persist = true;        // blocks stream their tiles (cross-tile pipelining)
     const long cap = slots[dev & 63];
     if (!sec) {
-        const long nblk = persist && total > cap ? cap : total;
+        const long nblk = total > cap ? cap : total;       // blocks stream their tiles (cross-tile pipelining)
         ConvArgsPair ap;
         ap.p[0] = a;
         ap.p[1] = a;
@@ -879,7 +878,7 @@ static int launch_conv(ConvArgs a, int B, hipStream_t st, const ConvSecond *sec 
     if (total1 > 0x7fffffffL) return DKT_E_SHAPE;
     b.total_tiles = (int)total1;
     long nb0 = total, nb1 = total1;
-    if (persist && total + total1 > cap) {
+    if (total + total1 > cap) {
         const double w0 = (double)total * a.nch16, w1 = (double)total1 * b.nch16;
         nb1 = (long)(cap * w1 / (w0 + w1) + 0.5);
         nb1 = nb1 < 1 ? 1 : (nb1 > total1 ? total1 : nb1);
@@ -899,183 +898,44 @@ static int launch_conv(ConvArgs a, int B, hipStream_t st, const ConvSecond *sec 
 #define CONV_HAVE_WS 1
 #endif
 
-// Tile shape by layer width and image size.  Wide layers put all four waves on the
-// channel axis (one block = up to 256 channels: each patch is staged once); narrow
-// layers put them on rows.  Images too small to give every CU a block with 4-row
-// wave tiles use 2-row wave tiles.
-template <int KS, int PASSES>
-static int launch_conv_shape(const ConvArgs &a, int B, hipStream_t st, const ConvSecond *sec = nullptr) {
-    const long tiles4 = (long)a.tiles_w * ((a.H + 3) / 4) * B;    // blocks if a block covers 4 rows
+// The launch of a tile conv_tile_select() chose, for one (filter size, pass count, NRM, DSC): the rows of CONV_TILE_TABLE
+// that exist for it, and only those, are instantiated.
+template <int KS, int PASSES, int NRM, int DSC>
+static int launch_conv_tile(const ConvTile &t, const ConvArgs &a, int B, hipStream_t st, const ConvSecond *sec) {
+#define CONV_TILE_CASE(WM_, WN_, NF_, MF_, ST_, CK_, K1_, NRM_, DSC_, PAIR_, P3_)                                            \
+    if constexpr ((KS == 3 || (K1_)) && (!NRM || (NRM_)) && (!DSC || (DSC_)) && (PASSES == 3 || !(P3_))) {                  \
+        if (t.WM == WM_ && t.WN == WN_ && t.NF == NF_ && t.MF == MF_ && t.ST == ST_ && t.CK == CK_ && (!sec || (PAIR_)))    \
+            return launch_conv<KS, WM_, WN_, NF_, PASSES, MF_, ST_, CK_, NRM, DSC>(a, B, st, sec);                          \
+    }
+    CONV_TILE_TABLE(CONV_TILE_CASE)
+#undef CONV_TILE_CASE
+    return DKT_E_UNSUPPORTED;
+}
+
+// The kernel instantiations are split by number of MFMA passes so that the build can compile them as parallel translation
+// units (dkt_stereo_amd/build.py: -DCONV_TU_PASSES=1|2|3, =4|5|6 the device-scaled instantiations of 1|2|3 passes, each
+// unit one specialisation of conv2d_launch_passes; =0 holds the tile selection, the ABI and the weight packer).  Compiled
+// without the macro this file is one complete translation unit.
+template <int PASSES, int DSC>
+int conv2d_launch_passes(const ConvTile &t, const ConvArgs &a, int B, hipStream_t st, const ConvSecond *sec);
+#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES != 0
+template <int PASSES, int DSC>
+int conv2d_launch_passes(const ConvTile &t, const ConvArgs &a, int B, hipStream_t st, const ConvSecond *sec) {
 #ifdef CONV_HAVE_WS
-    if constexpr (KS == 3 && PASSES == 3) {
-        if (!sec && conv_ws_eligible(a, B)) return launch_conv_ws(a, B, st);
+    if constexpr (PASSES == 3 && !DSC) {
+        if (t.kernel == CONV_KERNEL_WS) return launch_conv_ws(a, B, st);
     }
 #endif
-    if (a.in_norm) {
-        // instance norm + ReLU of the input folded into the staging: the second 3x3 layer of the feature
-        // encoder's residual blocks (core/extractor.py:46-50; 64, 96 and 128 channels) -- the same tile
-        // shapes as below, instantiated with NRM = 1
-        if constexpr (KS == 3) {
-            if (sec || a.nsrc != 1 || a.epi == 1 || a.epi == 2) return DKT_E_UNSUPPORTED;
-            if (a.Cout > 32 && a.Cout <= 64) {
-                if (tiles4 / 2 >= 512) return launch_conv<KS, 1, 4, 2, PASSES, 2, 1, 1, 1>(a, B, st);
-                return launch_conv<KS, 1, 4, 1, PASSES, 2, 1, 2, 1>(a, B, st);
-            }
-            if (a.Cout > 64 && a.Cout <= 96 && tiles4 >= CONV_FEW_TILES) return launch_conv<KS, 1, 4, 1, PASSES, 3, 1, 2, 1>(a, B, st);
-            if (a.Cout > 64 && a.Cout <= 128) {
-                if (tiles4 < CONV_FEW_TILES) return launch_conv<KS, 2, 2, 1, PASSES, 2, 1, 2, 1>(a, B, st);
-                return launch_conv<KS, 2, 2, 2, PASSES, 2, 1, 2, 1>(a, B, st);
-            }
-        }
-        return DKT_E_UNSUPPORTED;
+    if (t.KS == 1) return launch_conv_tile<1, PASSES, 0, DSC>(t, a, B, st, sec);
+    if constexpr (!DSC) {
+        if (a.in_norm) return launch_conv_tile<3, PASSES, 1, 0>(t, a, B, st, sec);
     }
-    // 4-row blocks keep the LDS stage at 65 KB, i.e. two blocks per CU; the 8-row forms
-    // (one block per CU) measured 15-35 % slower on every encoder layer (tools/_exp_enc.py).
-    // Small images (the 1/8 and 1/16 GRUs: 115 and 69 tiles of the default shape for 256 CUs)
-    // take half-height tiles so that twice as many CUs work.
-    const long few = CONV_FEW_TILES;
-    // the flow / disparity heads (2 and 1 output channels): a 32-channel wave tile halves the padded MFMA work
-    if (a.Cout <= 32) return launch_conv<KS, 1, 4, 1, PASSES, 1>(a, B, st, sec);  // 32 co x 4 rows
-    if (a.Cout <= 64) {
-        // 64 co x 8 rows with 16-channel chunks (33 KB LDS stage: still two blocks per CU): twice the
-        // MFMAs per weight fragment of the 4-row form (64->64 @368x624: 90 -> 78 us; not for images
-        // that give fewer 8-row tiles than resident blocks: @184x312 29 -> 32 us)
-        if constexpr (KS == 3) {
-            if (tiles4 / 2 >= 512) return launch_conv<KS, 1, 4, 2, PASSES, 2, 1, 1>(a, B, st, sec);   // >= one full wave of blocks
-        }
-        return launch_conv<KS, 1, 4, 1, PASSES>(a, B, st, sec);                          // 64 co x 4 rows
-    }
-    if (a.Cout <= 128) {
-        // 65 .. 96 channels: a 96-channel wave tile (three 32-channel blocks per wave, four waves on rows) instead of padding
-        // a quarter of the 128-channel tile's MFMAs and weight fragments: 96->96 @368x624 205 -> 181 us, two images 357 -> 330
-        if constexpr (KS == 3) {
-            if (a.Cout <= 96 && !sec && tiles4 >= few) return launch_conv<KS, 1, 4, 1, PASSES, 3>(a, B, st);
-        }
-        if (tiles4 < few) return launch_conv<KS, 2, 2, 1, PASSES>(a, B, st, sec);        // 128 co x 2 rows
-        return launch_conv<KS, 2, 2, 2, PASSES>(a, B, st, sec);                          // 128 co x 4 rows
-    }
-    // 257 .. 384 channels (the context encoder's 128 -> 3 x 128 projection, raft_stereo.py:103-106) on large images: four waves of
-    // 96 channels each and two rows -- the patch is staged once and no channel block is padding, where the 256-channel tile runs
-    // a second, half-empty block: 253 -> 213 us @184x312 (slower below ~500 tiles: 65 -> 70 us @92x156)
-    if constexpr (KS == 3) {
-        if (a.Cout > 256 && a.Cout <= 384 && !sec && (long)a.tiles_w * ((a.H + 1) / 2) * B >= 512)
-            return launch_conv<KS, 4, 1, 2, PASSES, 3>(a, B, st);
-    }
-    const long tiles2 = (long)a.tiles_w * ((a.H + 1) / 2) * B * ((a.Cout + 255) / 256);
-    if (tiles2 < few) return launch_conv<KS, 4, 1, 1, PASSES>(a, B, st, sec);            // 256 co x 1 row
-    // wide layers on large images: ONE block of 8 waves per CU, 256 co x 4 rows (WM x WN = 4 x 2): the two
-    // waves of a SIMD share their weight fragments through L1 and the patch halo shrinks (6 rows
-    // staged per 4 instead of 4 per 2).  Measured 384->256 @184x312: 326 -> 315 us; 128->256: 113 -> 109.
-    if (tiles4 * ((a.Cout + 255) / 256) >= 256) {
-        if constexpr (KS == 3) return launch_conv<KS, 4, 2, 2, PASSES>(a, B, st, sec);
-    }
-    // otherwise: 256 co x 2 rows per block, two blocks per CU.  (Measured on 384->256 @184x312:
-    // 324 us vs 374 us for the 256 co x 4 rows / one-block-per-CU form.)
-    return launch_conv<KS, 4, 1, 2, PASSES>(a, B, st, sec);                              // 256 co x 2 rows
+    return launch_conv_tile<3, PASSES, 0, DSC>(t, a, B, st, sec);
 }
-
-// Stride-2 layers (the encoders' down-sampling convolutions, core/extractor.py:16,34,136-138):
-// 2-row output tiles keep the (2*TR+1) x 65 input patch at 52 KB per LDS stage.
-template <int KS, int PASSES>
-static int launch_conv_stride2(const ConvArgs &a, int B, hipStream_t st) {
-    if constexpr (KS == 3 && PASSES == 3) {
-        // 128 co x 4 rows with 16-channel chunks (9 x 65 patch, 56 KB per stage, one block per CU): twice the MFMAs per weight
-        // fragment of the 2-row form -- 64->96 @736x1248 281 -> 243 us, two images 518 -> 422; 96->128 @368x624 x 2: 174 -> 138
-        if (a.Cout <= 128 && (long)a.tiles_w * ((a.Ho + 3) / 4) * B >= 512) {
-            // (up to 96 channels: the 96-channel wave tile, as for stride 1 -- 243 -> 223 us, two images 422 -> 395)
-            if (a.Cout <= 96) return launch_conv<KS, 1, 4, 1, PASSES, 3, 2, 1>(a, B, st);
-            return launch_conv<KS, 2, 2, 2, PASSES, 2, 2, 1>(a, B, st);
-        }
-    }
-    if (a.Cout <= 128) return launch_conv<KS, 2, 2, 1, PASSES, 2, 2>(a, B, st);   // 128 co x 2 rows
-    return launch_conv<KS, 4, 1, 1, PASSES, 2, 2>(a, B, st);                      // 256 co x 1 row
-}
-
-// The stride-1 selection of launch_conv_shape for the device-scaled kernel (dkt_conv2d_f16s_dscale: one problem, epilogue 0,
-// no input norm): the same thresholds, the same tile shapes -- a convolution and the input gradient of a layer of its size
-// run the same loop nest.  (The 64 -> 64 layers take the generic 64-channel tile, not conv_ws.h's weights-stationary kernel.)
-template <int KS, int PASSES>
-static int launch_conv_shape_dscale(const ConvArgs &a, int B, hipStream_t st) {
-    const long tiles4 = (long)a.tiles_w * ((a.H + 3) / 4) * B;
-    const long few = CONV_FEW_TILES;
-    if (a.Cout <= 32) return launch_conv<KS, 1, 4, 1, PASSES, 1, 1, 2, 0, 1>(a, B, st);
-    if (a.Cout <= 64) {
-        if constexpr (KS == 3) {
-            if (tiles4 / 2 >= 512) return launch_conv<KS, 1, 4, 2, PASSES, 2, 1, 1, 0, 1>(a, B, st);
-        }
-        return launch_conv<KS, 1, 4, 1, PASSES, 2, 1, 2, 0, 1>(a, B, st);
-    }
-    if (a.Cout <= 128) {
-        if constexpr (KS == 3) {
-            if (a.Cout <= 96 && tiles4 >= few) return launch_conv<KS, 1, 4, 1, PASSES, 3, 1, 2, 0, 1>(a, B, st);
-        }
-        if (tiles4 < few) return launch_conv<KS, 2, 2, 1, PASSES, 2, 1, 2, 0, 1>(a, B, st);
-        return launch_conv<KS, 2, 2, 2, PASSES, 2, 1, 2, 0, 1>(a, B, st);
-    }
-    if constexpr (KS == 3) {
-        if (a.Cout > 256 && a.Cout <= 384 && (long)a.tiles_w * ((a.H + 1) / 2) * B >= 512)
-            return launch_conv<KS, 4, 1, 2, PASSES, 3, 1, 2, 0, 1>(a, B, st);
-    }
-    const long tiles2 = (long)a.tiles_w * ((a.H + 1) / 2) * B * ((a.Cout + 255) / 256);
-    if (tiles2 < few) return launch_conv<KS, 4, 1, 1, PASSES, 2, 1, 2, 0, 1>(a, B, st);
-    if (tiles4 * ((a.Cout + 255) / 256) >= 256) {
-        if constexpr (KS == 3) return launch_conv<KS, 4, 2, 2, PASSES, 2, 1, 2, 0, 1>(a, B, st);
-    }
-    return launch_conv<KS, 4, 1, 2, PASSES, 2, 1, 2, 0, 1>(a, B, st);
-}
-
-// The kernel instantiations are split by number of MFMA passes so that the build can compile them as
-// parallel translation units (dkt_stereo_amd/build.py: -DCONV_TU_PASSES=1|2|3, =4|5|6 the device-scaled
-// instantiations of 1|2|3 passes; =0 holds the ABI and the weight packer).  Compiled without the macro this
-// file is one complete translation unit.
-int conv2d_launch_p1(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec);
-int conv2d_launch_p2(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec);
-int conv2d_launch_p3(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec);
-
-template <int PASSES>
-static int conv2d_launch_passes(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec) {
-    if (stride == 2) {
-        if (sec || a.in_norm) return DKT_E_UNSUPPORTED;
-        if (KH == 1) {
-            // 1x1, stride 2 = the 1x1 stride-1 layer on the even pixels of the even rows (see ConvArgs::src_px)
-            ConvArgs v = a;
-            v.H = a.Ho; v.W = a.Wo;
-            v.src_px = 2; v.src_w = a.W; v.src_hw = (long)a.H * a.W;
-            return launch_conv_shape<1, PASSES>(v, B, st, nullptr);
-        }
-
-        if (KH == 3) return launch_conv_stride2<3, PASSES>(a, B, st);
-        return launch_conv_stride2<1, PASSES>(a, B, st);
-    }
-    if (KH == 3) return launch_conv_shape<3, PASSES>(a, B, st, sec);
-    return launch_conv_shape<1, PASSES>(a, B, st, sec);
-}
-#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 1
-int conv2d_launch_p1(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec) { return conv2d_launch_passes<1>(a, B, KH, stride, st, sec); }
 #endif
-#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 2
-int conv2d_launch_p2(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec) { return conv2d_launch_passes<2>(a, B, KH, stride, st, sec); }
-#endif
-#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 3
-int conv2d_launch_p3(const ConvArgs &a, int B, int KH, int stride, hipStream_t st, const ConvSecond *sec) { return conv2d_launch_passes<3>(a, B, KH, stride, st, sec); }
-#endif
-
-int conv2d_launch_dscale_p1(const ConvArgs &a, int B, int KH, hipStream_t st);
-int conv2d_launch_dscale_p2(const ConvArgs &a, int B, int KH, hipStream_t st);
-int conv2d_launch_dscale_p3(const ConvArgs &a, int B, int KH, hipStream_t st);
-template <int PASSES>
-static int conv2d_launch_dscale(const ConvArgs &a, int B, int KH, hipStream_t st) {
-    if (KH == 3) return launch_conv_shape_dscale<3, PASSES>(a, B, st);
-    return launch_conv_shape_dscale<1, PASSES>(a, B, st);
-}
-#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 4
-int conv2d_launch_dscale_p1(const ConvArgs &a, int B, int KH, hipStream_t st) { return conv2d_launch_dscale<1>(a, B, KH, st); }
-#endif
-#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 5
-int conv2d_launch_dscale_p2(const ConvArgs &a, int B, int KH, hipStream_t st) { return conv2d_launch_dscale<2>(a, B, KH, st); }
-#endif
-#if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 6
-int conv2d_launch_dscale_p3(const ConvArgs &a, int B, int KH, hipStream_t st) { return conv2d_launch_dscale<3>(a, B, KH, st); }
+#if defined(CONV_TU_PASSES) && CONV_TU_PASSES != 0
+template int conv2d_launch_passes<(CONV_TU_PASSES - 1) % 3 + 1, (CONV_TU_PASSES > 3)>(const ConvTile &, const ConvArgs &, int, hipStream_t,
+                                                                                     const ConvSecond *);
 #endif
 
 #if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 0
@@ -1094,10 +954,8 @@ static int conv_fill(ConvArgs &a, const float *const *src, const int *src_channe
                      int B, int H, int W, int Cout, int KH, int KW, int relu, int passes,
                      const ConvEpilogue *epi, int stride) {
     if (!src || !src_channels || !src_bstride || !w_hi || !w_lo || !out) return DKT_E_NULL;
-    if (stride != 1 && (stride != 2 || epi)) return DKT_E_UNSUPPORTED;
-    if (nsrc < 1 || nsrc > CONV_MAX_SRC || B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || B > 65535) return DKT_E_SHAPE;
-    if (KH != KW || (KH != 1 && KH != 3)) return DKT_E_UNSUPPORTED;
-    if (passes < 1 || passes > 3) return DKT_E_UNSUPPORTED;
+    const int rc = conv_query_check(stride, epi ? epi->kind : 0, nsrc, B, H, W, Cout, KH, KW, passes);
+    if (rc != DKT_OK) return rc;
     if (!(in_scale > 0.0f) || !(out_scale > 0.0f)) return DKT_E_SHAPE;
     for (int s = 0; s < CONV_MAX_SRC; ++s) {
         a.src[s] = s < nsrc ? src[s] : nullptr;
@@ -1141,10 +999,22 @@ static int conv_fill(ConvArgs &a, const float *const *src, const int *src_channe
     return DKT_OK;
 }
 
-static int conv_dispatch(const ConvArgs &a, int B, int KH, int stride, int passes, hipStream_t st, const ConvSecond *sec) {
-    if (passes == 3) return conv2d_launch_p3(a, B, KH, stride, st, sec);
-    if (passes == 2) return conv2d_launch_p2(a, B, KH, stride, st, sec);
-    return conv2d_launch_p1(a, B, KH, stride, st, sec);
+// One filled argument block (or two: sec) to its launch: the tile is chosen before the device is entered.
+static int conv_run(ConvArgs &a, int B, int KH, int stride, int passes, int form, int device, void *stream,
+                    const ConvSecond *sec = nullptr) {
+    ConvTile t;
+    const int rc = conv_tile_select({KH, stride, passes, a.Cout, a.nsrc, a.src_ch, a.epi, B, a.H, a.W, form}, &t);
+    if (rc != DKT_OK) return rc;
+    DKT_ENTER(device);
+    if (stride == 2 && t.ST == 1) {       // the sub-sampled source of a 1x1 stride-2 layer (see ConvArgs::src_px)
+        a.src_px = 2; a.src_w = a.W; a.src_hw = (long)a.H * a.W;
+        a.H = a.Ho; a.W = a.Wo;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    const bool dsc = form == CONV_FORM_DSCALE;
+    if (passes == 3) return dsc ? conv2d_launch_passes<3, 1>(t, a, B, st, sec) : conv2d_launch_passes<3, 0>(t, a, B, st, sec);
+    if (passes == 2) return dsc ? conv2d_launch_passes<2, 1>(t, a, B, st, sec) : conv2d_launch_passes<2, 0>(t, a, B, st, sec);
+    return dsc ? conv2d_launch_passes<1, 1>(t, a, B, st, sec) : conv2d_launch_passes<1, 0>(t, a, B, st, sec);
 }
 
 static int conv2d_f16s_impl(const float *const *src, const int *src_channels, const long *src_bstride,
@@ -1156,8 +1026,7 @@ static int conv2d_f16s_impl(const float *const *src, const int *src_channels, co
     const int rc = conv_fill(a, src, src_channels, src_bstride, nsrc, w_hi, w_lo, bias, out_scale, in_scale, out,
                              out_bstride, B, H, W, Cout, KH, KW, relu, passes, epi, stride);
     if (rc != DKT_OK) return rc;
-    DKT_ENTER(device);
-    return conv_dispatch(a, B, KH, stride, passes, (hipStream_t)stream, nullptr);
+    return conv_run(a, B, KH, stride, passes, CONV_FORM_SINGLE, device, stream);
 }
 
 // ---- two convolutions in one launch (descriptor form) ----
@@ -1186,15 +1055,9 @@ static int conv_fill_desc(ConvArgs &a, const dkt_conv_desc *d, int passes) {
         a.stats_ws = d->stats_ws;
         a.stats_part = (double *)d->stats_part;
     }
-    if (d->in_norm) {
-        if (d->nsrc != 1 || d->KH != 3 || d->Cout <= 32 || d->Cout > 128 || d->epilogue == 1 || d->epilogue == 2)
-            return DKT_E_UNSUPPORTED;
-        a.in_norm = d->in_norm;
-    }
+    a.in_norm = d->in_norm;         // (what the in-norm form supports: conv_tile_select)
     return DKT_OK;
 }
-
-static int conv_width_class(int Cout) { return Cout <= 32 ? 0 : Cout <= 64 ? 1 : Cout <= 128 ? 2 : 3; }
 
 extern "C" long dkt_conv2d_stats_ws_floats(int B, int Cout, int Ho, int Wo) {
     if (B <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return DKT_E_SHAPE;
@@ -1204,12 +1067,20 @@ extern "C" long dkt_conv2d_stats_ws_floats(int B, int Cout, int Ho, int Wo) {
     return (long)B * ((Wo + 31) / 32) * ((Ho + 7) / 8 * 8) * Cout * 2;
 }
 
+extern "C" int dkt_conv2d_f16s_tile(int KS, int stride, int passes, int Cout, const int *src_channels, int nsrc, int epilogue,
+                                    int B, int H, int W, int form, int *tile) {
+    if (!tile) return DKT_E_NULL;
+    ConvTile t;
+    const int rc = conv_tile_select({KS, stride, passes, Cout, nsrc, src_channels, epilogue, B, H, W, form}, &t);
+    if (rc == DKT_OK) memcpy(tile, &t, sizeof t);        // eight integers, in the order of the struct
+    return rc;
+}
+
 extern "C" int dkt_conv2d_f16s_desc(const dkt_conv_desc *p, int passes, int device, void *stream) {
     ConvArgs a;
     const int rc = conv_fill_desc(a, p, passes);
     if (rc != DKT_OK) return rc;
-    DKT_ENTER(device);
-    return conv_dispatch(a, p->B, p->KH, p->stride == 2 ? 2 : 1, passes, (hipStream_t)stream, nullptr);
+    return conv_run(a, p->B, p->KH, p->stride == 2 ? 2 : 1, passes, p->in_norm ? CONV_FORM_NORM : CONV_FORM_SINGLE, device, stream);
 }
 
 extern "C" int dkt_conv2d_f16s_pair(const dkt_conv_desc *p0, const dkt_conv_desc *p1, int passes, int device, void *stream) {
@@ -1223,8 +1094,7 @@ extern "C" int dkt_conv2d_f16s_pair(const dkt_conv_desc *p0, const dkt_conv_desc
     sec.B = p1->B;
     // both problems run one kernel instantiation: same filter size and the same output-width class
     if (p0->KH != p1->KH || conv_width_class(p0->Cout) != conv_width_class(p1->Cout)) return DKT_E_UNSUPPORTED;
-    DKT_ENTER(device);
-    return conv_dispatch(a, p0->B, p0->KH, 1, passes, (hipStream_t)stream, &sec);
+    return conv_run(a, p0->B, p0->KH, 1, passes, CONV_FORM_PAIR, device, stream, &sec);
 }
 
 extern "C" int dkt_conv2d_f16s(const float *const *src, const int *src_channels, const long *src_bstride,
@@ -1246,10 +1116,7 @@ extern "C" int dkt_conv2d_f16s_dscale(const float *const *src, const int *src_ch
                              out_bstride, B, H, W, Cout, KH, KW, 0, passes, nullptr, 1);
     if (rc != DKT_OK) return rc;
     a.in_norm = scale;         // DSC: in_scale = scale[0], out_scale = w_inv_scale * scale[1], both read by the kernel
-    DKT_ENTER(device);
-    if (passes == 3) return conv2d_launch_dscale_p3(a, B, KH, (hipStream_t)stream);
-    if (passes == 2) return conv2d_launch_dscale_p2(a, B, KH, (hipStream_t)stream);
-    return conv2d_launch_dscale_p1(a, B, KH, (hipStream_t)stream);
+    return conv_run(a, B, KH, 1, passes, CONV_FORM_DSCALE, device, stream);
 }
 
 extern "C" int dkt_conv2d_f16s_strided(const float *const *src, const int *src_channels, const long *src_bstride,

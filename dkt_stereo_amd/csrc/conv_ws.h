@@ -444,23 +444,7 @@ __global__ __launch_bounds__(256, 1) void conv64_ws_kernel(ConvArgs a) {
     }
 }
 
-// 64 -> 64, 3x3, stride 1, one 64-channel source, epilogues 0 / 3: images with at least 192 tiles (8 x 32 pixels) take the
-// weights-stationary kernel (DKT_CONV_WS=0 keeps the streaming kernel: A/B and bit-identity tests of the round-2 path)
-static bool conv_ws_enabled() {
-    const char *e = getenv("DKT_CONV_WS");      // read per launch: the tests compare both kernels in one process
-    return !(e && e[0] == '0');
-}
-
-static bool conv_ws_eligible(const ConvArgs &a, int B) {
-    if (!conv_ws_enabled()) return false;
-    if (a.nsrc != 1 || a.src_ch[0] != 64 || a.Cout != 64 || a.nch16 != 4 || a.CoutPad != 64) return false;
-    if (a.epi != 0 && a.epi != 3) return false;
-    if (a.Ho != a.H || a.Wo != a.W || B > 64) return false;
-    if ((long)a.H * a.W * 128 > 0x7fffffffL) return false;     // 32 output planes per buffer descriptor, byte offsets in 32 bits
-    const long tiles = (long)a.tiles_w * ((a.H + 7) / 8) * B;
-    return tiles >= 192;           // measured: 22 against 30 us at 230 tiles (184 x 312), equal at 128, 35 against 45-48 at 512
-}
-
+// (which calls come here: conv_tile.h -- 64 -> 64, 3x3, stride 1, one 64-channel source, epilogues 0 / 3, B <= 64)
 static int launch_conv_ws(ConvArgs a, int B, hipStream_t st) {
     constexpr int STAGE = 10 * 34 * 12 * 2;
     const size_t lds = ((size_t)2 * STAGE + 8) * sizeof(unsigned) + (a.in_norm ? (size_t)B * 512 : 0);

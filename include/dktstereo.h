@@ -576,6 +576,18 @@ int dkt_conv2d_f16s_pair(const dkt_conv_desc *p0, const dkt_conv_desc *p1, int p
  *   in_norm   : see the field. */
 int dkt_conv2d_f16s_desc(const dkt_conv_desc *p, int passes, int device, void *stream);
 
+/* Which kernel and tile shape a dkt_conv2d_f16s* call of these sizes runs on (core/update.py:9-10, 19-21, 72-76, 111-113;
+ * core/extractor.py:16,34): the answer of the function every launch asks (csrc/conv_tile.h), for the tests -- no device is
+ * touched and no tensor pointer read.  KS the filter size (1 or 3), stride 1 or 2, H, W the INPUT size, epilogue as in
+ * dkt_conv_desc, form: 0 = one problem, 1 = the first problem of dkt_conv2d_f16s_pair, 2 = with in_norm,
+ * 3 = dkt_conv2d_f16s_dscale.  DKT_CONV_WS is read per call, as by a launch.
+ *   tile[8] = {kernel (0 = conv2d_f16s_kernel, 1 = the weights-stationary 64 -> 64 kernel), KS, WM, WN, NF, MF, ST, CK}:
+ *   WM x WN waves along (channels, rows), each 32*MF channels x NF rows x 32 columns, stride ST, 16*CK-channel chunks.  KS
+ *   and ST are what the kernel runs at: a 1x1 stride-2 layer reports ST = 1 (a stride-1 layer on a sub-sampled source).
+ * Returns DKT_OK, or the code the launch of such a call returns (tile is left alone); tile or src_channels null DKT_E_NULL. */
+int dkt_conv2d_f16s_tile(int KS, int stride, int passes, int Cout, const int *src_channels, int nsrc, int epilogue,
+                         int B, int H, int W, int form, int *tile /* int[8] */);
+
 /* The 7x7 stems (Cin <= 4, stride 1, padding 3: core/update.py:75, igev_stereo/update.py:81,
  * core/extractor.py:136) on the fp16 matrix cores with split operands (stem7.hip): K laid out
  * over (dy, dx, ci) instead of 32-channel chunks.  Weights are pre-packed once per layer

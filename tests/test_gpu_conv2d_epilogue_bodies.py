@@ -21,6 +21,14 @@ import torch
 import torch.nn.functional as F
 
 from test_gpu_parity import DEV
+from test_host_conv2d_tile import DSCALE, NORM, layer_tile
+
+#: what dkt_conv2d_f16s_tile answers, (kernel, KS, WM, WN, NF, MF, ST, CK), for the shapes the cases are named after
+TILE_8WAVE = (0, 3, 4, 2, 2, 2, 1, 2)         # 256 channels x 4 rows, 8 waves
+TILE_4X96 = (0, 3, 4, 1, 2, 3, 1, 2)          # four waves of 96 channels x 2 rows
+TILE_256_FEW = (0, 3, 4, 1, 1, 2, 1, 2)       # 256 channels x 1 row
+TILE_96_4ROWS = (0, 3, 1, 4, 1, 3, 1, 2)      # the 96-channel wave tile, four waves on rows
+TILE_128_FEW = (0, 3, 2, 2, 1, 2, 1, 2)       # 128 channels x 2 rows
 
 pytestmark = pytest.mark.gpu
 
@@ -85,7 +93,8 @@ def test_ragged_channel_blocks(case, relu):
 
 # ---- the wide tile shapes ---------------------------------------------------------------------------------------------------
 #: name, (B, Cin, H, W), Cout: 8 waves (>= 256 four-row tiles), four waves of 96 channels (>= 512 two-row tiles), few tiles
-WIDE = [("128_256_8wave", (4, 128, 64, 128), 256), ("128_384_96ch", (4, 128, 64, 128), 384), ("128_256_few", (1, 128, 23, 39), 256)]
+WIDE = [("128_256_8wave", (4, 128, 64, 128), 256, TILE_8WAVE), ("128_384_96ch", (4, 128, 64, 128), 384, TILE_4X96),
+        ("128_256_few", (1, 128, 23, 39), 256, TILE_256_FEW)]
 
 
 @torch.no_grad()
@@ -93,7 +102,7 @@ WIDE = [("128_256_8wave", (4, 128, 64, 128), 256), ("128_384_96ch", (4, 128, 64,
 def test_wide_tiles(case):
     from dkt_stereo_amd import conv
     with conv.use_backend("f16x3"):
-        name, shape, cout = case
+        name, shape, cout, want_tile = case
         B, _, H, W = shape
         tiles_w = (W + 31) // 32
         if name == "128_256_8wave":
@@ -105,6 +114,7 @@ def test_wide_tiles(case):
         layer = _layer(shape[1], cout, 3, 1, 31)
         x, _ = _input(shape, 31)
         assert conv.hip_eligible(layer)
+        assert layer_tile(shape, layer) == want_tile
         for relu in (False, True):
             got = conv.conv2d(x, layer, relu=relu)
             _close(got, _ref64(x, layer, relu))
@@ -135,6 +145,7 @@ def test_many_tiles_conv2d_and_fused():
         layer, x, res = m["layer"], m["x"], m["res"]
         assert conv.hip_eligible(layer) and conv.fused_eligible(layer)
         assert ((520 + 31) // 32) * ((70 + 3) // 4) * 2 == 612
+        assert layer_tile(x.shape, layer) == layer_tile(x.shape, layer, epilogue=3) == TILE_96_4ROWS      # plain and residual join
         for relu in (False, True):
             got = conv.conv2d(x, layer, relu=relu)
             _close(got, m["ref"].clamp_min(0) if relu else m["ref"])
@@ -156,6 +167,7 @@ def test_many_tiles_conv2d_stats(normed):
         m = _many()
         layer, x = m["layer"], m["x"]
         assert conv.stats_eligible(layer) and conv.fused_eligible(layer, True)
+        assert layer_tile(x.shape, layer, form=NORM if normed else 0) == TILE_96_4ROWS
         params = extractor.instance_norm_params(torch.nn.InstanceNorm2d(96), x) if normed else None
         ref = m["ref_n"] if normed else m["ref"]
         out, st = conv.conv2d_stats(x, layer, in_norm=params)
@@ -247,7 +259,8 @@ def test_gate_q_alone_in_a_pair_and_in_place():
 
 
 # ---- stride 2, and the 1x1 stride-2 layer run on every second pixel of every second row ------------------------------------
-STRIDE2 = [("3x3_s2_96_128", (1, 96, 47, 81), 128, 3), ("1x1_s2_64_96", (2, 64, 90, 130), 96, 1)]
+#: (the tiles: 128 channels x 2 rows at stride 2; the 1x1 layer as a stride-1 layer, ST = 1, on the 45 x 65 output)
+STRIDE2 = [("3x3_s2_96_128", (1, 96, 47, 81), 128, 3, (0, 3, 2, 2, 1, 2, 2, 2)), ("1x1_s2_64_96", (2, 64, 90, 130), 96, 1, (0, 1, 2, 2, 1, 2, 1, 2))]
 
 
 @torch.no_grad()
@@ -256,10 +269,11 @@ STRIDE2 = [("3x3_s2_96_128", (1, 96, 47, 81), 128, 3), ("1x1_s2_64_96", (2, 64, 
 def test_stride2_and_subsampled_sources(case, relu):
     from dkt_stereo_amd import conv
     with conv.use_backend("f16x3"):
-        _, shape, cout, k = case
+        _, shape, cout, k, want_tile = case
         layer = _layer(shape[1], cout, k, 2, 61)
         x, _ = _input(shape, 61)
         assert conv.hip_eligible(layer)
+        assert layer_tile(shape, layer) == want_tile
         got = conv.conv2d(x, layer, relu=relu)
         assert tuple(got.shape[2:]) == ((shape[2] - 1) // 2 + 1, (shape[3] - 1) // 2 + 1)
         _close(got, _ref64(x, layer, relu))
@@ -277,6 +291,7 @@ def test_device_scaled_form(magnitude):
         x, _ = _input((2, 96, 24, 60), 71)
         x = x * magnitude
         assert conv.hip_eligible(layer) and not conv.few_eligible(layer) and not conv.direct_eligible(layer)
+        assert layer_tile(x.shape, layer, form=DSCALE) == TILE_128_FEW          # 24 four-row tiles: the half-height form
         g, _, scale = conv.conv_grad_prepass(x, want_bias=False)
         got = conv.conv2d_dscale(g, layer, scale)
         ref = _ref64(x, layer, bias=False)

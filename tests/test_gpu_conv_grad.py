@@ -14,9 +14,16 @@ import torch.nn as nn
 
 import _conv_grad_ref as R
 import _synth
+from test_host_conv2d_tile import DSCALE, tile
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+
+
+#: the tile of each case's input-gradient convolution (Cout -> Cin channels, device-scaled form), as dkt_conv2d_f16s_tile names
+#: it: the 32-channel head tile, the 64-channel four-row tile (3x3 and 1x1, and of a 2-channel gradient), 256 channels x 1 row
+DGRAD_TILES = dict(zip(R.CASES, [(0, 1, 1, 4, 1, 1, 1, 2), (0, 3, 1, 4, 1, 2, 1, 2), (0, 1, 1, 4, 1, 2, 1, 2), (0, 3, 1, 4, 1, 2, 1, 2),
+                                 (0, 3, 4, 1, 1, 2, 1, 2)]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -74,6 +81,8 @@ def test_node_against_truth(case, relu, layout, k):
     y0, gp, gb, gx, gw = _ref(case, relu)
     s = 2.0 ** k
     gy = R.laid_out(R.inputs(case)[3] * s, layout, DEV)
+    B, H, W, ks, cin, cout = case
+    assert tile(ks, 1, 3, cin, (cout,), 0, B, H, W, DSCALE) == DGRAD_TILES[case]
     y, got_gx, got_gw, got_gb = _node(case, relu, gy)
     assert torch.equal(y.cpu(), y0)
     e_gx = R.gx_error(got_gx.cpu(), gx * s)

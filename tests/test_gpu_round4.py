@@ -452,7 +452,7 @@ def test_weights_stationary_conv_is_reproducible_and_gated(monkeypatch):
 
 @pytest.mark.parametrize("cout", [96, 72])
 def test_ninety_six_channel_tile_matches_fp64_in_every_form(cout):
-    """65 .. 96 output channels run on a 96-channel wave tile (conv2d.hip: launch_conv<3, 1, 4, 1, P, 3>): plain / ReLU /
+    """65 .. 96 output channels run on a 96-channel wave tile (conv_tile.h: the row 1, 4, 1, 3 of the table): plain / ReLU /
     residual join / instance-norm input + output statistics against fp64 (the layers of core/extractor.py's layer2)."""
     import torch.nn as nn
     from dkt_stereo_amd import conv

@@ -36,6 +36,7 @@ def build(subs):
     open(os.path.join(OUT, "conv_ws.h"), "w").write(ws)
     src = open(os.path.join(B.CSRC, "conv2d.hip")).read()
     src = src.replace('#include "dkt_common.h"', '#include "%s/dkt_common.h"' % B.CSRC)
+    src = src.replace('#include "conv_tile.h"', '#include "%s/conv_tile.h"' % B.CSRC)
     src = src.replace('#include "conv_ws.h"', '#include "%s/conv_ws.h"' % OUT)
     path = os.path.join(OUT, "conv2d_ws_trace.hip")
     open(path, "w").write(src)
