@@ -178,6 +178,9 @@ SIGNATURES = {
     "dkt_context_upsample_bwd": [_vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "dkt_context_upsample_logits_fwd": [_vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
     "dkt_context_upsample_logits_bwd": [_vp, _l, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
+    "dkt_soft_argmin_fwd": [_vp, _l, _f, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "dkt_soft_argmin_bwd": [_vp, _l, _vp, _l, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "dkt_soft_argmin_bwd_workspace": [_i, _i, _i, _i, _i],
     "dkt_corr1d_lookup_bwd": [_vp, _vp, _l, _pp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_geo_lookup_bwd": [_vp, _vp, _vp, _pp, _pp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_geo_pool_bwd": [_pp, _vp, _l, _i, _l, _i, _i, _vp],
@@ -251,7 +254,7 @@ SIGNATURES = {
     "dkt_interp_bilinear_bwd": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }
 #: entry points that do not return an int status
-RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long, "dkt_adamw_workspace": ctypes.c_long}
+RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long, "dkt_adamw_workspace": ctypes.c_long, "dkt_soft_argmin_bwd_workspace": ctypes.c_long}
 
 #: DKT_E_UNSUPPORTED of include/dktstereo.h
 E_UNSUPPORTED = -7

@@ -20,7 +20,8 @@ What runs where (inference, ``test_mode=True``):
   * 3-D aggregation (dres0-4, classif3): dense Conv3d / ConvTranspose3d on the vendor library (out of
     this library's scope, SURVEY.md 8a-13), eval-mode BatchNorm3d folded into the weights;
   * soft-argmin: trilinear x4 up-sampling, softmax over the 192 disparities, expectation
-    (gwcnet/submodules.py:18-22).
+    (gwcnet/submodules.py:18-22) in one launch, dkt_soft_argmin_fwd (SOFT_ARGMIN_HIP; in train() one autograd node
+    per head, backward dkt_soft_argmin_bwd).
 """
 from types import SimpleNamespace
 
@@ -29,7 +30,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .extractor import conv_norm_act
+from .soft_argmin import soft_argmin
 from .submodule import build_gwc_concat_volume, build_gwc_volume
+
+#: A/B handle: True runs the disparity heads on dkt_soft_argmin_fwd / _bwd, False on the reference's torch
+#: lines (what a CPU tensor or maxdisp > SOFT_ARGMIN_MAX_D gets in any case)
+SOFT_ARGMIN_HIP = True
+#: the kernels stage at most 64 coarse planes: f D <= 256
+SOFT_ARGMIN_MAX_D = 256
 
 
 def convbn(cin, cout, k, stride, pad, dilation):
@@ -198,8 +206,12 @@ class GWCNet(nn.Module):
         pass
 
     def _predict(self, classif, out):
-        """classif -> x4 trilinear -> softmax -> soft-argmin, negated: gwc_main.py:250-268."""
+        """classif -> x4 trilinear -> softmax -> soft-argmin, negated: gwc_main.py:250-268 (training) and :270-276 (eval).
+        One launch (soft_argmin.hip; under autograd one node that saves the cost alone) when SOFT_ARGMIN_HIP is on, the
+        cost is on a HIP device and maxdisp <= 256; else the reference's torch lines."""
         cost = classif[2](_cbn3(classif[0], out, True))
+        if SOFT_ARGMIN_HIP and cost.is_cuda and 4 * cost.shape[2] == self.maxdisp <= SOFT_ARGMIN_MAX_D:
+            return soft_argmin(cost, 4, -1.0).to(cost.dtype)        # (computed in fp32; the torch lines return the cost's dtype)
         cost = F.interpolate(cost, scale_factor=4, mode='trilinear', align_corners=False)
         pred = F.softmax(torch.squeeze(cost, 1), dim=1)
         return -disparity_regression(pred, self.maxdisp).unsqueeze(1)
@@ -215,11 +227,7 @@ class GWCNet(nn.Module):
             out3 = self.dres4(out2)
             return [self._predict(self.classif0, c0), self._predict(self.classif1, out1),
                     self._predict(self.classif2, out2), self._predict(self.classif3, out3)]
-        out3 = self.dres4(self.dres3(self.dres2(c0)))
-        cost3 = self.classif3[2](_cbn3(self.classif3[0], out3, True))
-        cost3 = F.interpolate(cost3, scale_factor=4, mode='trilinear', align_corners=False)
-        pred3 = F.softmax(torch.squeeze(cost3, 1), dim=1)
-        return -disparity_regression(pred3, self.maxdisp).unsqueeze(1)
+        return self._predict(self.classif3, self.dres4(self.dres3(self.dres2(c0))))
 
     def build_volume(self, featL, featR):
         """gwc_main.py:310-317."""

@@ -178,6 +178,36 @@ int dkt_context_upsample_logits_bwd(const float *gout, long gout_bstride, const 
                                     float scale, float *gdisp, float *glogits, float *ws, int B, int h, int w, int device,
                                     void *stream);
 
+/* ---- soft-argmin heads ------------------------------------------------------------------ */
+
+/* GwcNet's disparity head (meta_arch/gwcnet/gwc_main.py:246-276: F.interpolate(cost, scale_factor=4, mode='trilinear',
+ * align_corners=False), F.softmax over the planes, disparity_regression of gwcnet/submodules.py:18-22) and, at factor 1,
+ * IGEV's initial disparity (meta_arch/igev_stereo/igev_stereo.py:175-176: F.softmax over the 48 planes and
+ * disparity_regression) in one launch.  cost (B,Dc,h,w): batch stride cost_bstride elements, the other dimensions
+ * contiguous; factor f in {1,4}, D = f*Dc, H = f*h, W = f*w; out (B,1,H,W) contiguous:
+ *   out[b,0,Y,X] = out_scale * sum_d d * softmax_d(up(cost))[b,d,Y,X]
+ * up: per axis of coarse length n, fine index o reads i0 = floor(src), i1 = min(i0+1, n-1) at lambda = src - i0 with
+ * src = max(0, (o+0.5)/f - 0.5): at f = 4, o = 4q+j: (i0, lambda) = (q-1,.625), (q-1,.875), (q,.125), (q,.375); f = 1 is the
+ * identity.  The softmax is shifted by the maximum of the pixel's fine logits, summed in ascending d.  The up-sampled
+ * volume is never stored.
+ * Errors (all three entries): a null pointer the call needs DKT_E_NULL; B, Dc, h, w <= 0 or a batch stride shorter than
+ * one image DKT_E_SHAPE; factor outside {1,4}, D > 256, B > 65535, H*W > 2^31 - 257 or H > 524280 DKT_E_UNSUPPORTED; a
+ * pointer that is not a multiple of 4 bytes DKT_E_ALIGN. */
+int dkt_soft_argmin_fwd(const float *cost, long cost_bstride, float out_scale, float *out, int B, int Dc, int h, int w,
+                        int factor, int device, void *stream);
+
+/* Its backward (torch autograd through the lines above), the softmax recomputed from cost: with p_d the softmax, E its
+ * expectation and z_d the fine logits, dL/dz_d = out_scale * gout * p_d * (d - E), carried to gcost (B,Dc,h,w), contiguous,
+ * through the transpose of the three interpolations.  gout (B,1,H,W): batch stride gout_bstride elements.  Deterministic
+ * (no atomics, one owner per element, fixed summation orders).  factor 4: two launches; ws holds the gradient of every
+ * output pixel's blended coarse column, dkt_soft_argmin_bwd_workspace bytes.  factor 1: one launch, ws unused (may be null). */
+int dkt_soft_argmin_bwd(const float *gout, long gout_bstride, const float *cost, long cost_bstride, float out_scale,
+                        float *gcost, void *ws, int B, int Dc, int h, int w, int factor, int device, void *stream);
+
+/* Bytes of ws: 4*B*Dc*H*W at factor 4 (a quarter of the up-sampled volume), 0 at factor 1; negative = the error code the
+ * other two entries return for these sizes. */
+long dkt_soft_argmin_bwd_workspace(int B, int Dc, int h, int w, int factor);
+
 /* ---- backward of lookup / pyramid (autograd of core/corr.py:119-146) -------- */
 
 /* Gradient of every pyramid level from the gradient of one lookup's output:
