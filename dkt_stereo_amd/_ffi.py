@@ -135,6 +135,28 @@ class SeqLossGrad(ctypes.Structure):
     """dkt_seq_loss_grad of include/dktstereo.h."""
     _fields_ = [("grad", ctypes.c_void_p * LOSS_MAX_PRED), ("grad_loss", ctypes.c_void_p * 2)]
 
+
+#: DKT_NS_MAX_PRED, DKT_NS_REC of include/dktstereo.h
+NS_MAX_PRED, NS_REC = 64, 72
+
+
+class NsLossDesc(ctypes.Structure):
+    """dkt_ns_loss_desc of include/dktstereo.h."""
+    _fields_ = [("pred", ctypes.c_void_p * NS_MAX_PRED), ("pred_bstride", ctypes.c_long * NS_MAX_PRED),
+                ("weight", ctypes.c_float * NS_MAX_PRED), ("n", ctypes.c_int),
+                ("im", ctypes.c_void_p * 3), ("im_bstride", ctypes.c_long * 3),
+                ("conf", ctypes.c_void_p), ("conf_bstride", ctypes.c_long),
+                ("target", ctypes.c_void_p), ("target_bstride", ctypes.c_long), ("valid_in", ctypes.c_void_p),
+                ("conf_threshold", ctypes.c_float), ("max_flow", ctypes.c_float), ("alpha_disp", ctypes.c_float),
+                ("alpha_photo", ctypes.c_float), ("valid", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("planes", ctypes.c_void_p), ("loss", ctypes.c_void_p), ("rec", ctypes.c_void_p),
+                ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int)]
+
+
+class NsLossGrad(ctypes.Structure):
+    """dkt_ns_loss_grad of include/dktstereo.h."""
+    _fields_ = [("grad", ctypes.c_void_p * NS_MAX_PRED), ("grad_loss", ctypes.c_void_p)]
+
 # name -> argtypes, mirrors include/dktstereo.h one to one
 SIGNATURES = {
     "dkt_loop_status": [ctypes.POINTER(C8RangeJob), _i, _vp, _l, _vp, _vp, _i, _vp],
@@ -142,6 +164,9 @@ SIGNATURES = {
     "dkt_seq_loss_ws_doubles": [_i, _i, _i, _i, _i],
     "dkt_seq_loss": [ctypes.POINTER(SeqLossDesc), _vp, _i, _vp],
     "dkt_seq_loss_bwd": [ctypes.POINTER(SeqLossDesc), ctypes.POINTER(SeqLossGrad), _i, _vp],
+    "dkt_ns_loss_workspace": [_i, _i, _i],
+    "dkt_ns_loss": [ctypes.POINTER(NsLossDesc), _vp, _i, _vp],
+    "dkt_ns_loss_bwd": [ctypes.POINTER(NsLossDesc), ctypes.POINTER(NsLossGrad), _i, _vp],
     "dkt_motion_front_c8": [ctypes.POINTER(MotionFrontDesc), _i, _vp],
     "dkt_resample_pair_c8": [ctypes.POINTER(ResampleC8Job), ctypes.POINTER(ResampleC8Job), _i, _vp],
     "dkt_gru_c8_flag_words": [_i, _i, _i],
@@ -254,7 +279,7 @@ SIGNATURES = {
     "dkt_interp_bilinear_bwd": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }
 #: entry points that do not return an int status
-RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long, "dkt_adamw_workspace": ctypes.c_long, "dkt_soft_argmin_bwd_workspace": ctypes.c_long}
+RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long, "dkt_adamw_workspace": ctypes.c_long, "dkt_soft_argmin_bwd_workspace": ctypes.c_long, "dkt_ns_loss_workspace": ctypes.c_long}
 
 #: DKT_E_UNSUPPORTED of include/dktstereo.h
 E_UNSUPPORTED = -7

@@ -1036,6 +1036,65 @@ typedef struct dkt_seq_loss_grad {
 } dkt_seq_loss_grad;
 int dkt_seq_loss_bwd(const dkt_seq_loss_desc *d, const dkt_seq_loss_grad *g, int device, void *stream);
 
+/* ---- NeRF-supervised loss (csrc/ns_loss.hip) ---------------------------------------------------------------------------
+ * Replaces ns_loss (meta_arch/nerf_stereo/loss.py:128-181) with everything it calls: disp_warp (:73-84, mesh_grid :38-44,
+ * norm_grid :29-36), SSIM (:5-27), photometric_loss (:86-90) and trinocular_loss (:92-109), for n predictions.
+ *   With target: conf' = conf * (target < 0); valid = (conf' > conf_threshold) & (sqrt(target^2) < max_flow), written to
+ *   `valid` as bool (B,H,W); the photometric weight is 1 - conf'; disparity term mean_i = mean over valid of |p_i - target| conf'.
+ *   Without target (null; trinocular_loss alone): conf is the weight as given, valid_in (B,H,W bytes, contiguous) the mask,
+ *   there is no disparity term.
+ *   Warp: view im[0] is sampled at x + d, im[2] at x - d (d = p_i, negative), grid_sample with align_corners=False after
+ *   norm_grid's (W-1, H-1) normalisation: px = (x + s d) W/(W-1) - 0.5, py = y H/(H-1) - 0.5; border padding for the image,
+ *   zero padding for the mask (a sampled plane of ones); reconstruction = mask * sample.
+ *   p(view) = 0.15 mean_c |im[1] - rec| + 0.85 mean_c clamp((1 - SSIM(rec, im[1]))/2, 0, 1), SSIM over 7 x 7 windows of the
+ *   ReflectionPad2d(3)-padded planes; loss_warp = min(p12, p23); loss_2 the same from the unwarped views;
+ *   automask = (loss_warp < loss_2) & valid; photo_i = mean over automask of loss_warp * weight.
+ *   loss = alpha_disp * sum_i weight[i] mean_i + alpha_photo * sum_i weight[i] photo_i, each sum accumulated in fp32 in order
+ *   i (weight[i] already fp32); without target, loss = alpha_photo * sum_i weight[i] photo_i.  alpha_photo == 0 skips the
+ *   photometric term (:164-167) and `state` may be null.  The mean of an empty set is NaN, as torch's is.
+ * state: n x (B,H,W) bytes, out: bit 0 the automask, bit 1 set where the third view (im[2]) won the minimum.
+ * planes: null, or (3,B,H,W) floats, out: p12, p23 and loss_2 of prediction 0 (the handle of the tests).
+ * rec (DKT_NS_REC doubles), written by the finalize launch: rec[0] = number of valid pixels, rec[1] = fl32 EPE mean of
+ * prediction n-1 over valid, rec[2..4] = fl32 fractions of EPE < 1, 3, 5, rec[5] = 1 when some prediction holds a NaN or an
+ * Inf (:155), rec[6], rec[7] = the two weighted sums, rec[8 + i] = automask count of prediction i.
+ * pred[i]: (B,1,H,W) with contiguous H x W planes and batch stride pred_bstride[i] (views such as [:, :1] are read in
+ * place).  im[k]: (B,3,H,W), the three planes of an image contiguous.  conf, target: (B,H,W) with batch strides.
+ * ws: dkt_ns_loss_workspace(B, H, W) bytes (block partials and the loss_2 plane; it does not depend on n), 8-byte aligned.
+ * Forward: three launches (loss_2 and valid once; one tiled launch over (tile, image, prediction); finalize); backward: one
+ * launch after it on the same stream, reading state and rec on the device.  fp64 partials in a fixed order, no atomics:
+ * bit-identical from run to run.  No host synchronisation.
+ *   grad[i] (B,1,H,W) contiguous: every element stored exactly once; g = *grad_loss (device scalar).
+ * Errors (every entry, before any device call): a null desc / ws / pointer the call needs DKT_E_NULL; B, H, W <= 0, H or W
+ * < 4 (ReflectionPad2d(3)), n outside 1..DKT_NS_MAX_PRED or a batch stride shorter than an image DKT_E_SHAPE; H*W > 2^31 - 257
+ * or B*n > 65535 DKT_E_UNSUPPORTED; a float pointer that is not a multiple of 4 bytes, ws or rec of 8, DKT_E_ALIGN.
+ * dkt_ns_loss_workspace returns DKT_E_SHAPE for B <= 0, H < 4 or W < 4. */
+#define DKT_NS_MAX_PRED 64
+#define DKT_NS_REC 72
+typedef struct dkt_ns_loss_desc {
+    const float *pred[DKT_NS_MAX_PRED];
+    long pred_bstride[DKT_NS_MAX_PRED];
+    float weight[DKT_NS_MAX_PRED];
+    int n;
+    const float *im[3]; long im_bstride[3];
+    const float *conf; long conf_bstride;
+    const float *target; long target_bstride;   /* or null */
+    const unsigned char *valid_in;              /* with target == null */
+    float conf_threshold, max_flow, alpha_disp, alpha_photo;
+    unsigned char *valid;                       /* out, with target != null */
+    unsigned char *state;                       /* out */
+    float *planes;                              /* out, or null */
+    float *loss;                                /* out, device scalar */
+    double *rec;                                /* out */
+    int B, H, W;
+} dkt_ns_loss_desc;
+typedef struct dkt_ns_loss_grad {
+    float *grad[DKT_NS_MAX_PRED];
+    const float *grad_loss;
+} dkt_ns_loss_grad;
+long dkt_ns_loss_workspace(int B, int H, int W);
+int dkt_ns_loss(const dkt_ns_loss_desc *d, void *ws, int device, void *stream);
+int dkt_ns_loss_bwd(const dkt_ns_loss_desc *d, const dkt_ns_loss_grad *g, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
