@@ -17,6 +17,7 @@
 // for the 16-byte and the 4-byte path alike.  The maximum is taken on the bit patterns of |g'| (an unsigned maximum orders
 // finite < Inf < NaN), so a non-finite gradient is seen as such.
 #include "gru_gates.h"
+#include "wave_reduce.h"
 
 #define PRE_SEG 4096          // elements per work item: 4 x float4 per thread
 #define PRE_K (PRE_SEG / 1024)
@@ -91,11 +92,8 @@ __global__ __launch_bounds__(256) void conv_grad_prepass_kernel(PrepassArgs a) {
             }
         }
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            sum = __fadd_rn(sum, __shfl_xor(sum, d, 64));
-            const unsigned o = (unsigned)__shfl_xor((int)amax, d, 64);
-            amax = o > amax ? o : amax;
-        }
+        for (int d = 32; d >= 1; d >>= 1) sum = __fadd_rn(sum, __shfl_xor(sum, d, 64));
+        amax = wave_max(amax);
         if (lane == 0) {
             wsum[wave] = sum;
             wmax[wave] = amax;
@@ -134,15 +132,8 @@ __global__ __launch_bounds__(256) void conv_grad_prepass_finish_kernel(PrepassFi
         }
         if (a.gb) a.gb[c] = s;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned o = (unsigned)__shfl_xor((int)amax, d, 64);
-        amax = o > amax ? o : amax;
-    }
-    if ((tid & 63) == 0) wmax[tid >> 6] = amax;
-    __syncthreads();
+    amax = block_max<4>(amax, wmax);
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w) amax = wmax[w] > amax ? wmax[w] : amax;
         // e = 12 - floor(log2(amax)): amax * 2^e in [2^12, 2^13); clamped to +-DKT_CONV_GRAD_MAX_EXP (a subnormal amax lands
         // on the clamp); amax == 0, Inf or NaN: e = 0 -- a non-finite gradient then reaches the convolution unscaled and
         // comes out non-finite, as the format's contract says

@@ -11,6 +11,7 @@
 // each line below is one torch elementwise op of the reference, in its order, with its fp32 rounding.  Multiplications by
 // a 0/1 mask are kept as multiplications: 0 * NaN = NaN and 0 * -x = -0 are what the reference computes.
 #include "dkt_common.h"
+#include "wave_reduce.h"
 
 #include <math.h>
 
@@ -31,17 +32,6 @@ __device__ __forceinline__ float fande_consistent(float s, float t, float tau) {
     return sqrtf(__fmul_rn(d, d)) < tau ? 1.0f : 0.0f;
 }
 
-__device__ __forceinline__ double fande_block_sum(double v, double *red) {
-    for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int i = 1; i < FANDE_THREADS / 64; ++i) s += red[i];
-    return s;
-}
-
 __global__ __launch_bounds__(FANDE_THREADS) void fande_count_kernel(FandeArgs a, double *__restrict__ ws) {
     __shared__ double red[FANDE_THREADS / 64];
     const dkt_fande_job &j = a.job[blockIdx.z];
@@ -56,8 +46,8 @@ __global__ __launch_bounds__(FANDE_THREADS) void fande_count_kernel(FandeArgs a,
         nvc += (double)__fmul_rn(fande_consistent(src[r], tgt[r], j.tau), v);
         nv += (double)v;
     }
-    nvc = fande_block_sum(nvc, red);
-    nv = fande_block_sum(nv, red);
+    nvc = block_sum<FANDE_THREADS / 64>(nvc, red);
+    nv = block_sum<FANDE_THREADS / 64>(nv, red);
     if (threadIdx.x == 0) {
         double *o = ws + (((long)blockIdx.z * a.B + b) * FANDE_NB + blockIdx.x) * 2;
         o[0] = nvc;
@@ -73,8 +63,8 @@ __global__ __launch_bounds__(FANDE_THREADS) void fande_apply_kernel(FandeArgs a,
     if (j.filter == 2) {
         // prob_threshold = num_valid_consistent / num_valid (fp32 tensors; exact counts for 0/1 masks), prob < prob_threshold
         const double *p = ws + ((long)blockIdx.z * a.B + b) * FANDE_NB * 2;
-        const double nvc = fande_block_sum(p[threadIdx.x * 2], red);
-        const double nv = fande_block_sum(p[threadIdx.x * 2 + 1], red);
+        const double nvc = block_sum<FANDE_THREADS / 64>(p[threadIdx.x * 2], red);
+        const double nv = block_sum<FANDE_THREADS / 64>(p[threadIdx.x * 2 + 1], red);
         const float thr = __fdiv_rn((float)nvc, (float)nv);
         select = j.rand[b] < thr ? 1.0f : 0.0f;
     }

@@ -8,8 +8,8 @@
 // partial sums, several blocks per plane so that 128 planes still fill 256 CUs) and one
 // normalise(+ReLU) pass.
 #include "dkt_common.h"
-
-#define IN_SPLIT_MAX 64
+#include "norm_split.h"
+#include "wave_reduce.h"
 
 __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float *__restrict__ x,
                                                              double *__restrict__ part, long HW, int S) {
@@ -33,21 +33,12 @@ __global__ __launch_bounds__(256) void instnorm_stats_kernel(const float *__rest
             sq += (double)v * v;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o);
-        sq += __shfl_down(sq, o);
-    }
     __shared__ double red[2][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][w] = sum;
-        red[1][w] = sq;
-    }
-    __syncthreads();
+    sum = block_sum<4>(sum, red[0]);
+    sq = block_sum<4>(sq, red[1]);
     if (threadIdx.x == 0) {
-        part[((long)plane * S + s) * 2] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        part[((long)plane * S + s) * 2 + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        part[((long)plane * S + s) * 2] = sum;
+        part[((long)plane * S + s) * 2 + 1] = sq;
     }
 }
 
@@ -88,34 +79,7 @@ __global__ __launch_bounds__(256) void instnorm_apply_kernel(const float *__rest
 
 extern "C" long dkt_instance_norm_workspace(int planes, long HW) {
     if (planes <= 0 || HW <= 0) return DKT_E_SHAPE;
-    return (long)planes * IN_SPLIT_MAX * 2 * (long)sizeof(double);
-}
-
-static int instnorm_split(int planes, long HW) {
-    int S = (2048 + planes - 1) / planes;          // ~2048 blocks in flight
-    const long max_split = (HW + 4095) / 4096;      // at least 4096 elements per block
-    if (S > max_split) S = (int)max_split;
-    if (S > IN_SPLIT_MAX) S = IN_SPLIT_MAX;
-    if (S < 1) S = 1;
-    return S;
-}
-
-// (sum, sum of squares) of one block, in fp64, returned to every thread; `red` is reused across calls
-__device__ __forceinline__ void block_sum2(double &sum, double &sq, double (*red)[4]) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_down(sum, o);
-        sq += __shfl_down(sq, o);
-    }
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();                     // (a previous call's readers are done with `red`)
-    if (lane == 0) {
-        red[0][w] = sum;
-        red[1][w] = sq;
-    }
-    __syncthreads();
-    sum = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    sq = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    return (long)planes * NORM_SPLIT_MAX * 2 * (long)sizeof(double);
 }
 
 // Statistics accumulated by a convolution's epilogue (conv2d.hip, ConvArgs.stats_ws: per (batch, entry, channel) fp32 sums
@@ -138,7 +102,8 @@ __global__ __launch_bounds__(256) void conv_stats_reduce_kernel(const float *__r
         sum += (double)v.x;
         sq += (double)v.y;
     }
-    block_sum2(sum, sq, red);
+    sum = block_sum<4>(sum, red[0]);
+    sq = block_sum<4>(sq, red[1]);
     const double mean = sum / (double)HW, var = sq / (double)HW - mean * mean;
     if (!(mean * mean <= CONV_STATS_TRUST * var)) {         // block-uniform (also true for a NaN or a negative variance)
         const float *p = out + (long)b * out_bs + (long)c * HW;
@@ -156,7 +121,8 @@ __global__ __launch_bounds__(256) void conv_stats_reduce_kernel(const float *__r
                 sq += v * v;
             }
         }
-        block_sum2(sum, sq, red);
+        sum = block_sum<4>(sum, red[0]);
+        sq = block_sum<4>(sq, red[1]);
     }
     for (int s = threadIdx.x; s < S; s += 256) {
         part[((long)plane * S + s) * 2] = s ? 0.0 : sum;
@@ -168,7 +134,7 @@ int conv_stats_reduce(const float *ws, double *part, int B, int C, long entries,
                       hipStream_t st) {
     const long planes = (long)B * C;
     if (planes <= 0 || planes > 65535 || entries <= 0) return DKT_E_SHAPE;
-    const int S = instnorm_split((int)planes, HW);
+    const int S = norm_split((int)planes, HW);
     hipLaunchKernelGGL(conv_stats_reduce_kernel, dim3((unsigned)planes), dim3(256), 0, st, ws, part, C, entries, S, out,
                        out_bs, HW);
     return dkt_launch_status();
@@ -178,7 +144,7 @@ extern "C" int dkt_instance_norm_stats(const float *x, void *workspace, int plan
     if (!x || !workspace) return DKT_E_NULL;
     if (planes <= 0 || HW <= 0 || planes > 65535) return DKT_E_SHAPE;
     DKT_ENTER(device);
-    const int S = instnorm_split(planes, HW);
+    const int S = norm_split(planes, HW);
     hipLaunchKernelGGL(instnorm_stats_kernel, dim3((unsigned)S, (unsigned)planes), dim3(256), 0, (hipStream_t)stream,
                        x, (double *)workspace, HW, S);
     return dkt_launch_status();
@@ -191,7 +157,7 @@ extern "C" int dkt_instance_norm(const float *x, float *y, void *workspace, int 
     int rc = dkt_instance_norm_stats(x, workspace, planes, HW, device, stream);
     if (rc) return rc;
     DKT_ENTER(device);
-    const int S = instnorm_split(planes, HW);
+    const int S = norm_split(planes, HW);
     hipLaunchKernelGGL(instnorm_apply_kernel, dim3((unsigned)S, (unsigned)planes), dim3(256), 0, (hipStream_t)stream,
                        x, y, (const double *)workspace, HW, S, eps, relu ? 1 : 0, S);
     return dkt_launch_status();
@@ -221,7 +187,7 @@ extern "C" int dkt_instance_norm_finalize(const void *workspace, int planes, lon
     if (!workspace || !mean_invstd) return DKT_E_NULL;
     if (planes <= 0 || HW <= 0 || planes > 65535) return DKT_E_SHAPE;
     DKT_ENTER(device);
-    const int S = instnorm_split(planes, HW);
+    const int S = norm_split(planes, HW);
     hipLaunchKernelGGL(instnorm_finalize_kernel, dim3((unsigned)((planes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const double *)workspace, mean_invstd, planes, HW, S, eps);
     return dkt_launch_status();
@@ -277,7 +243,7 @@ static int instnorm_add_relu_impl(const float *a, const float *a_norm, int a_rel
     if (!a || !c || !y || !workspace) return DKT_E_NULL;
     if (planes <= 0 || HW <= 0 || planes > 65535) return DKT_E_SHAPE;
     DKT_ENTER(device);
-    const int S = instnorm_split(planes, HW);
+    const int S = norm_split(planes, HW);
     hipLaunchKernelGGL(instnorm_add_relu_kernel, dim3((unsigned)S, (unsigned)planes), dim3(256), 0, (hipStream_t)stream,
                        a, c, y, (const double *)workspace, HW, S, eps, S, a_norm, a_relu ? 1 : 0);
     return dkt_launch_status();

@@ -20,18 +20,8 @@
 // The join without a gradient for c (gc == NULL) needs no sums: one launch writes ga.
 // Plain scalar fp32 (no packed math: DESIGN 3.4).
 #include "dkt_common.h"
-
-#define INB_SPLIT_MAX 64
-
-// blocks per plane of the sums launch: the rule of norm.hip's instnorm_split
-static int inb_split(int planes, long HW) {
-    int S = (2048 + planes - 1) / planes;          // ~2048 blocks in flight
-    const long max_split = (HW + 4095) / 4096;      // at least 4096 elements per block
-    if (S > max_split) S = (int)max_split;
-    if (S > INB_SPLIT_MAX) S = INB_SPLIT_MAX;
-    if (S < 1) S = 1;
-    return S;
-}
+#include "norm_split.h"
+#include "wave_reduce.h"
 
 enum { INB_NORM = 0, INB_NORM_RELU = 1, INB_JOIN = 2 };
 
@@ -80,21 +70,12 @@ __global__ __launch_bounds__(256) void inb_sums_kernel(const float *__restrict__
             sgy += (double)g * (double)yh;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        sg += __shfl_down(sg, d);
-        sgy += __shfl_down(sgy, d);
-    }
     __shared__ double red[2][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][w] = sg;
-        red[1][w] = sgy;
-    }
-    __syncthreads();
+    sg = block_sum<4>(sg, red[0]);
+    sgy = block_sum<4>(sgy, red[1]);
     if (threadIdx.x == 0) {
-        part[((long)plane * S + s) * 2] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        part[((long)plane * S + s) * 2 + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        part[((long)plane * S + s) * 2] = sg;
+        part[((long)plane * S + s) * 2 + 1] = sgy;
     }
 }
 
@@ -191,7 +172,7 @@ __global__ __launch_bounds__(256) void inb_join_apply_kernel(const float *__rest
 
 extern "C" long dkt_instance_norm_bwd_workspace(int planes, long HW) {
     if (planes <= 0 || HW <= 0) return DKT_E_SHAPE;
-    return (long)planes * inb_split(planes, HW) * 2 * (long)sizeof(double);
+    return (long)planes * norm_split(planes, HW) * 2 * (long)sizeof(double);
 }
 
 extern "C" int dkt_instance_norm_bwd(const float *gy, const float *x, const float *mean_invstd, int relu, float *gx,
@@ -200,7 +181,7 @@ extern "C" int dkt_instance_norm_bwd(const float *gy, const float *x, const floa
     if (planes <= 0 || HW <= 0 || planes > 65535) return DKT_E_SHAPE;
     DKT_ENTER(device);
     hipStream_t st = (hipStream_t)stream;
-    const int S = inb_split(planes, HW);
+    const int S = norm_split(planes, HW);
     const dim3 grid((unsigned)S, (unsigned)planes);
     double *part = (double *)workspace;
     if (relu) {
@@ -225,7 +206,7 @@ extern "C" int dkt_instance_norm_add_relu_bwd(const float *gout, const float *ou
     if (planes <= 0 || HW <= 0 || planes > 65535) return DKT_E_SHAPE;
     DKT_ENTER(device);
     hipStream_t st = (hipStream_t)stream;
-    const int S = inb_split(planes, HW);
+    const int S = norm_split(planes, HW);
     const dim3 grid((unsigned)S, (unsigned)planes);
     double *part = (double *)workspace;
     if (!gc) {                                      // only `a` needs a gradient: no sums, one launch

@@ -18,6 +18,7 @@
 // and every pixel gathers them over its windows (more than once where reflection folds the border back onto it), adds the L1
 // term and multiplies by d(mask * sample)/d px * s * W/(W-1).  No atomics; every gradient element is stored exactly once.
 #include "dkt_common.h"
+#include "wave_reduce.h"
 
 #include <math.h>
 
@@ -34,11 +35,6 @@
 #define NS_C2 9e-4f
 
 static inline int ns_tiles(int n) { return (n + NS_T - 1) / NS_T; }
-
-__device__ __forceinline__ double ns_wave_sum(double v) {
-    for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh, 64);
-    return v;
-}
 
 // ReflectionPad2d's source index (|offset| <= 3 < n), clamped so that positions never used still read inside the image
 __device__ __forceinline__ int ns_refl(int i, int n) {
@@ -290,7 +286,7 @@ __global__ __launch_bounds__(NS_THREADS) void ns_fwd_kernel(dkt_ns_loss_desc d, 
     }
 #pragma unroll
     for (int k = 0; k < NS_QP + 5; ++k) {
-        const double s = ns_wave_sum(q[k]);
+        const double s = wave_sum(q[k]);
         if (lane == 0) part[wave][k] = s;
     }
     __syncthreads();
@@ -308,14 +304,9 @@ __global__ __launch_bounds__(NS_FIN_THREADS) void ns_finalize_kernel(dkt_ns_loss
     __shared__ double tot[NS_Q];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int R = NS_Q0 + NS_QP * d.n;
-    // one wave per quantity; lane l sums blocks l, l + 64, ... in order, then the fixed shuffle tree
+    // one wave per quantity, summed over the blocks in wave_reduce.h's column order (rows 5 .. NS_Q0 - 1 are unused: 0)
     for (int k = wave; k < R; k += NS_FIN_THREADS / 64) {
-        double s = 0.0;
-        if (k < 5 || k >= NS_Q0) {
-            const double *p = ws + (long)k * nblk;
-            for (int j = lane; j < nblk; j += 64) s += p[j];
-        }
-        s = ns_wave_sum(s);
+        const double s = column_sum(ws + (long)k * nblk, k < 5 || k >= NS_Q0 ? nblk : 0);
         if (lane == 0) tot[k] = s;
     }
     __syncthreads();

@@ -1,11 +1,9 @@
 // dkt_adamw_step: the optimizer step of tools/ft_dkt.py:243-246 (AdamW of :58),
 //     scaler.unscale_(optimizer); clip_grad_norm_(model.parameters(), 1.0); scaler.step(optimizer)
 // for every parameter of the model in at most three launches and without a host read.  The parameters are a list of tensors
-// of arbitrary sizes; device tables of pointers (p, g, exp_avg, exp_avg_sq) and a table of count + 1 exclusive prefix
-// offsets flatten them, as in ema.hip, and the grid strides over fixed tiles of OPT_TILE elements of that flat range.  A
-// tile inside one tensor keeps eight loads of each operand in flight per thread; a tile across a boundary walks element by
-// element.  The loads are dwords, coalesced across the wave: a tensor boundary may fall on any element, so no wider access
-// is aligned in general.
+// of arbitrary sizes behind device tables of pointers (p, g, exp_avg, exp_avg_sq) and of offsets; the walk over fixed tiles
+// of OPT_TILE elements is flat_walk.h's, the fixed-order sums are wave_reduce.h's, and the kernels below hold their
+// element arithmetic.
 //
 // (a) adamw_norm_kernel     partial[tile] = sum of g^2 over the tile, in fp64 (each square is exact in fp64; the 2048 terms
 //                           are added thread, wave, block in a fixed tree), so the value belongs to the TILE and does not depend
@@ -28,11 +26,12 @@
 //                               p' = p1 - step_size * (m' / denom)
 //                           (torch.optim.AdamW's single-tensor sequence: mul_, lerp_, mul_/addcmul_, sqrt/div/add_, addcdiv_.)
 //                           g is NOT rewritten: the clipped gradient exists in registers only.  absmax (optional): max |p'| per
-//                           tensor by the integer atomic max of ema.hip (max|p| of the unchanged tensor on a skipped step).
+//                           tensor by the integer atomic max of flat_walk.h (max|p| of the unchanged tensor on a skipped step).
 // Without clipping, scaling and found_inf only (c) runs: it takes t = counter + 1, and the block that finishes last (an
 // integer ticket) stores the counter and the record {-1, 1, 0, 1}.  No float atomics anywhere: every output is bit-identical
 // from run to run and for every grid size.  Memory traffic: 28 B per parameter in (c), 4 B in (a), plus the tables.
 #include "dkt_common.h"
+#include "flat_walk.h"
 
 #include <math.h>
 
@@ -61,72 +60,46 @@ struct AdamwArgs {
     int full;                     // (a) and (b) have run: record and the counter are theirs
 };
 
-// the tensor holding flat element e: the largest k with off[k] <= e (empty tensors have off[k] == off[k+1] and are skipped)
-__device__ __forceinline__ int opt_tensor_of(const long *__restrict__ off, int count, long e) {
-    int lo = 0, hi = count - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= e) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
-
-// sum over the block in a fixed tree: lanes by xor-shuffle, then the four waves in order.  Valid in thread 0.
-__device__ __forceinline__ double opt_block_sum(double x, double *red) {
-    for (int sh = 32; sh > 0; sh >>= 1) x += __shfl_xor(x, sh, 64);
-    const int tid = threadIdx.x;
-    if ((tid & 63) == 0) red[tid >> 6] = x;
-    __syncthreads();
-    double s = red[0];
-    for (int w = 1; w < OPT_THREADS / 64; ++w) s += red[w];
-    __syncthreads();              // (red is reused)
-    return s;
-}
-
 __global__ __launch_bounds__(OPT_THREADS) void adamw_norm_kernel(const float *const *__restrict__ gp, const long *__restrict__ off,
                                                                int count, double *__restrict__ partial, int *__restrict__ nonfinite) {
     __shared__ double red[OPT_THREADS / 64];
     __shared__ int bad_any;
-    const long total = off[count];
-    const long tiles = (total + OPT_TILE - 1) / OPT_TILE;
     const int tid = threadIdx.x;
     if (tid == 0) bad_any = 0;
     __syncthreads();
     int bad = 0;
-    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long base = tile * OPT_TILE;
-        const long end = base + OPT_TILE < total ? base + OPT_TILE : total;
-        int k = opt_tensor_of(off, count, base);
-        float x[OPT_ITEMS];
-        if (off[k + 1] >= end) {
+    float x[OPT_ITEMS];           // the thread's items of the current tile; 0 where it has none
+#pragma unroll
+    for (int j = 0; j < OPT_ITEMS; ++j) x[j] = 0.f;
+    // x[] is all zero whenever a tile starts: done() zeroes every slot it has read, so a boundary tile that leaves its
+    // loop early (element() fills only the slots the thread has) still sums zeros for the rest
+    flat_walk<OPT_THREADS, OPT_ITEMS>(
+        off, count, nullptr, nullptr,
+        [&](int k, long base, long end) {
             const float *__restrict__ g = gp[k] - off[k];
 #pragma unroll
             for (int j = 0; j < OPT_ITEMS; ++j) {
                 const long e = base + j * OPT_THREADS + tid;
                 x[j] = e < end ? g[e] : 0.f;
             }
-        } else {
+            return 0u;
+        },
+        [&](int k, long i, int j) {
+            x[j] = gp[k][i];          // (not squared here: the loads of a boundary tile stay in flight together)
+            return 0u;
+        },
+        [&](long tile) {
+            double acc = 0.0;
 #pragma unroll
             for (int j = 0; j < OPT_ITEMS; ++j) {
-                const long e = base + j * OPT_THREADS + tid;
+                const double d = (double)x[j];
+                acc += d * d;
+                bad |= !isfinite(x[j]);
                 x[j] = 0.f;
-                if (e < end) {
-                    while (e >= off[k + 1]) ++k;
-                    x[j] = gp[k][e - off[k]];
-                }
             }
-        }
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < OPT_ITEMS; ++j) {
-            const double d = (double)x[j];
-            acc += d * d;
-            bad |= !isfinite(x[j]);
-        }
-        const double s = opt_block_sum(acc, red);
-        if (tid == 0) partial[tile] = s;
-    }
+            const double s = block_sum<OPT_THREADS / 64>(acc, red);
+            if (tid == 0) partial[tile] = s;
+        });
     if (bad) bad_any = 1;         // (any writer writes the same value)
     __syncthreads();
     if (tid == 0 && bad_any) atomicOr(nonfinite, 1);
@@ -138,7 +111,7 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_finalize_kernel(AdamwArgs a
     const long tiles = (total + OPT_TILE - 1) / OPT_TILE;
     double acc = 0.0;
     for (long i = threadIdx.x; i < tiles; i += OPT_THREADS) acc += a.partial[i];
-    const double sum = opt_block_sum(acc, red);
+    const double sum = block_sum<OPT_THREADS / 64>(acc, red);
     if (threadIdx.x == 0) {
         float inv = a.inv_scale;
         if (a.grad_scale) inv = (float)((double)a.inv_scale * (1.0 / (double)*a.grad_scale));
@@ -187,21 +160,6 @@ __device__ __forceinline__ float adamw_element(float &p, float g, float &m, floa
     return fabsf(pn);
 }
 
-__device__ __forceinline__ void opt_wave_max(unsigned m, unsigned *red, unsigned *absmax, int k) {
-    const int tid = threadIdx.x;
-    for (int sh = 32; sh > 0; sh >>= 1) {
-        const unsigned x = (unsigned)__shfl_xor((int)m, sh, 64);
-        m = x > m ? x : m;
-    }
-    if ((tid & 63) == 0) red[tid >> 6] = m;
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < OPT_THREADS / 64; ++w) m = red[w] > m ? red[w] : m;
-        atomicMax(absmax + k, m);
-    }
-    __syncthreads();              // (red is reused by the next tile)
-}
-
 __global__ __launch_bounds__(OPT_THREADS) void adamw_update_kernel(AdamwArgs a) {
     __shared__ unsigned red[OPT_THREADS / 64];
     __shared__ AdamwConst sc;
@@ -238,16 +196,11 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_update_kernel(AdamwArgs a) 
     __syncthreads();
     const AdamwConst c = sc;
     const int skip = s_skip;
-    const long total = off[count];
-    const long tiles = (total + OPT_TILE - 1) / OPT_TILE;
     if (skip && !a.absmax) return;
-    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const long base = tile * OPT_TILE;
-        const long end = base + OPT_TILE < total ? base + OPT_TILE : total;
-        int k = opt_tensor_of(off, count, base);
-        const long o = off[k];
-        if (off[k + 1] >= end) {
-            // the whole tile is inside tensor k
+    flat_walk<OPT_THREADS, OPT_ITEMS>(
+        off, count, a.absmax, red,
+        [&](int k, long base, long end) {
+            const long o = off[k];
             float *__restrict__ p = a.p[k] - o;
             unsigned mx = 0;
             if (skip) {
@@ -283,34 +236,18 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_update_kernel(AdamwArgs a) 
                     }
                 }
             }
-            if (a.absmax) opt_wave_max(mx, red, a.absmax, k);
-        } else {
-            // a tile across tensor boundaries: each thread walks its elements in increasing order
-            unsigned mx = 0;
-            for (int j = 0; j < OPT_ITEMS; ++j) {
-                const long e = base + j * OPT_THREADS + tid;
-                if (e >= end) break;
-                while (e >= off[k + 1]) {
-                    if (a.absmax && mx) atomicMax(a.absmax + k, mx);
-                    mx = 0;
-                    ++k;
-                }
-                const long i = e - off[k];
-                unsigned u;
-                if (skip) {
-                    u = __float_as_uint(fabsf(a.p[k][i]));
-                } else {
-                    float xp = a.p[k][i], xm = a.m[k][i], xv = a.v[k][i];
-                    u = __float_as_uint(adamw_element(xp, a.g[k][i], xm, xv, c));
-                    a.p[k][i] = xp;
-                    a.m[k][i] = xm;
-                    a.v[k][i] = xv;
-                }
-                mx = u > mx ? u : mx;
-            }
-            if (a.absmax && mx) atomicMax(a.absmax + k, mx);
-        }
-    }
+            return mx;
+        },
+        [&](int k, long i, int) {
+            if (skip) return __float_as_uint(fabsf(a.p[k][i]));
+            float xp = a.p[k][i], xm = a.m[k][i], xv = a.v[k][i];
+            const unsigned u = __float_as_uint(adamw_element(xp, a.g[k][i], xm, xv, c));
+            a.p[k][i] = xp;
+            a.m[k][i] = xm;
+            a.v[k][i] = xv;
+            return u;
+        },
+        [](long) {});
     if (!a.full) {
         // the single-launch step: every block has read the counter before it takes its ticket; the last one stores it
         __syncthreads();
@@ -362,16 +299,8 @@ extern "C" int dkt_adamw_step(float *const *p, const float *const *g, float *con
     a.ticket = (unsigned *)workspace + 1;
     a.partial = (double *)((char *)workspace + OPT_WS_HEADER);
     a.full = max_norm >= 0.0 || grad_scale || found_inf || inv_scale != 1.f;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    // 8 blocks of 4 waves per CU, the CU's full occupancy, and never more blocks than tiles; `grid` > 0 overrides (tests)
-    const long tiles = (total + OPT_TILE - 1) / OPT_TILE;
-    long blocks = (long)cus * 8;
-    if (blocks > tiles) blocks = tiles;
-    if (grid > 0) blocks = grid;
-    if (blocks < 1) blocks = 1;
+    long blocks = flat_walk_blocks((total + OPT_TILE - 1) / OPT_TILE);
+    if (grid > 0) blocks = grid;          // (tests)
     if (a.full) {
         hipLaunchKernelGGL(adamw_norm_kernel, dim3((unsigned)blocks), dim3(OPT_THREADS), 0, st, g, n, count, a.partial, a.nonfinite);
         hipLaunchKernelGGL(adamw_finalize_kernel, dim3(1), dim3(OPT_THREADS), 0, st, a);

@@ -9,6 +9,7 @@
 // one pass: maxima as fp16 bit patterns of |hi| (monotone for non-negative values; a NaN pattern is larger than Inf's, so
 // neither can be missed), combined with one atomicMax per wave.
 #include "dkt_common.h"
+#include "wave_reduce.h"
 
 struct StatusArgs {
     dkt_c8_range_job job[DKT_STATUS_MAX_JOBS];
@@ -19,15 +20,6 @@ struct StatusArgs {
     int *err_word;
     unsigned *status;
 };
-
-__device__ __forceinline__ unsigned wave_max(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned u = (unsigned)__shfl_xor((int)v, o, 64);
-        v = u > v ? u : v;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(256) void loop_status_kernel(StatusArgs a) {
     const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -11,6 +11,7 @@
 //
 // Backward (one launch): the same tiles; reads the upstream gradients and the mask counts on the device.
 #include "dkt_common.h"
+#include "wave_reduce.h"
 
 #include <math.h>
 
@@ -23,20 +24,6 @@
 #define FIN_THREADS 1024
 
 static inline int loss_tiles(int H, int W) { return (int)(((long)H * W + LOSS_TILE - 1) / LOSS_TILE); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_or(unsigned long long v) {
-    for (int sh = 32; sh > 0; sh >>= 1) {
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, sh, 64);
-        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), sh, 64);
-        v |= ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 
 // the per-pixel term of the loss: |p - gt| (loss.py:25) or smooth-L1 with beta = 1 (F.smooth_l1_loss: 0.5 z z / beta or z - 0.5 beta)
 __device__ __forceinline__ float loss_term(int kind, float p, float g) {
@@ -169,20 +156,9 @@ __global__ __launch_bounds__(FIN_THREADS) void seq_loss_finalize_kernel(dkt_seq_
     const int QK = d.n + 5, K = d.ntargets, R = K * QK;
     if (tid < LOSS_FLAG_WORDS) flags[tid] = 0;
     __syncthreads();
-    // one wave per quantity; lane l sums blocks l, l + 64, ... in order, then the fixed shuffle tree
+    // one wave per quantity, summed over the blocks in wave_reduce.h's column order
     for (int q = wave; q < R; q += FIN_THREADS / 64) {
-        const double *p = ws + (long)q * nblk;
-        double s = 0.0;
-        int i = lane;
-        for (; i + 7 * 64 < nblk; i += 8 * 64) {        // eight loads in flight, added in the same order as one at a time
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[i + u * 64];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; i < nblk; i += 64) s += p[i];
-        s = wave_sum(s);
+        const double s = column_sum(ws + (long)q * nblk, nblk);
         if (lane == 0) tot[q] = s;
     }
     const unsigned long long *fw = (const unsigned long long *)(ws + (long)R * nblk);

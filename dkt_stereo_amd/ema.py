@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _ffi
+from ._flat_tables import flat_tables
 # (importing the modules that fill the caches registers their refreshers)
 from . import conv, conv_c8, corr, extractor, update      # noqa: F401
 from .wcache import DERIVED_HOOKS, NOT_WEIGHTS, PACK_HOOKS
@@ -111,34 +112,14 @@ class _Refresh:
         return out
 
 
-_TABLES = {}
-
-
-def _tables(dev, ts, ss):
-    """Device tables of dkt_ema_update for this list of parameters (cached: built once per parameter set)."""
-    key = (dev, tuple(t.data_ptr() for t in ts), tuple(s.data_ptr() for s in ss), tuple(t.numel() for t in ts))
-    hit = _TABLES.get(key)
-    if hit is None:
-        off = [0]
-        for t in ts:
-            off.append(off[-1] + t.numel())
-        hit = (torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64).to(dev),
-               torch.tensor([s.data_ptr() for s in ss], dtype=torch.int64).to(dev),
-               torch.tensor(off, dtype=torch.int64).to(dev))
-        if len(_TABLES) >= 16:
-            _TABLES.pop(next(iter(_TABLES)))
-        _TABLES[key] = hit
-    return hit
-
-
 def ema_kernel(ts, ss, decay, absmax=None):
     """t <- decay * t + (1 - decay) * s for lists of same-device, dense fp32 CUDA tensors, one launch (dkt_ema_update).
     `absmax`: optional (len(ts),) fp32 tensor receiving max|t_new| per tensor."""
     if not ts:
         return
     dev = ts[0].device
-    tp, sp, off = _tables(dev, ts, ss)
-    rc = _ffi.lib().dkt_ema_update(tp.data_ptr(), sp.data_ptr(), off.data_ptr(), len(ts), float(decay), float(1 - decay),
+    _, ptr, _ = flat_tables(dev, ts, ss)
+    rc = _ffi.lib().dkt_ema_update(ptr[0], ptr[1], ptr[2], len(ts), float(decay), float(1 - decay),
                                    None if absmax is None else absmax.data_ptr(), _ffi.device_of(ts[0]), _ffi.stream_of(ts[0]))
     _ffi.check(rc, "dkt_ema_update")
 

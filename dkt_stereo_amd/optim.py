@@ -37,31 +37,9 @@ import math
 import torch
 
 from . import _ffi
+from ._flat_tables import flat_tables
 
-_TABLES = {}
 _HYPER = ("lr", "betas", "eps", "weight_decay")
-
-
-def _tables(dev, lists):
-    """Device tables of dkt_adamw_step for these four lists of tensors (cached per set of addresses).  A miss is staged
-    through pinned memory and copied without blocking, so it does not synchronise either."""
-    sizes = tuple(t.numel() for t in lists[0])
-    key = (dev,) + tuple(tuple(t.data_ptr() for t in ts) for ts in lists) + (sizes,)
-    hit = _TABLES.get(key)
-    if hit is None:
-        off = [0]
-        for n in sizes:
-            off.append(off[-1] + n)
-        rows = [[t.data_ptr() for t in ts] for ts in lists] + [off[:-1]]
-        host = torch.tensor(rows, dtype=torch.int64).reshape(-1)
-        host = torch.cat([host, torch.tensor([off[-1]], dtype=torch.int64)]).pin_memory()
-        table = host.to(dev, non_blocking=True)
-        n = len(sizes)
-        hit = (table, [table[i * n:].data_ptr() for i in range(5)], off[-1])
-        if len(_TABLES) >= 16:
-            _TABLES.pop(next(iter(_TABLES)))
-        _TABLES[key] = hit
-    return hit
 
 
 def workspace_bytes(count, total):
@@ -78,7 +56,7 @@ def adamw_kernel(ps, gs, ms, vs, step, record, workspace, lr, betas=(0.9, 0.999)
     if not ps:
         return
     dev = ps[0].device
-    table, ptr, total = _tables(dev, (ps, gs, ms, vs))
+    _, ptr, total = flat_tables(dev, ps, gs, ms, vs)
     if workspace.numel() < workspace_bytes(len(ps), total):
         raise _ffi.DktError("dkt_adamw_step workspace too small")
     opt = lambda t: None if t is None else t.data_ptr()

@@ -78,7 +78,7 @@ def inputs(c):
 
 
 def split(planes, HW):
-    """Blocks per plane of the sums launch (csrc/norm_train.hip inb_split)."""
+    """Blocks per plane of the sums launch (csrc/norm_split.h norm_split)."""
     S = (2048 + planes - 1) // planes
     S = min(S, (HW + 4095) // 4096, SPLIT_MAX)
     return max(S, 1)
