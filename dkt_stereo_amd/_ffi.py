@@ -19,7 +19,6 @@ _i, _l, _f, _vp = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
 _d = ctypes.c_double
 _pp = ctypes.POINTER(ctypes.c_void_p)
 _ip = ctypes.POINTER(ctypes.c_int)
-_lp = ctypes.POINTER(ctypes.c_long)
 
 class ConvDesc(ctypes.Structure):
     """dkt_conv_desc of include/dktstereo.h."""
@@ -32,7 +31,7 @@ class ConvDesc(ctypes.Structure):
                 ("e1", ctypes.c_void_p), ("e1_bstride", ctypes.c_long), ("h", ctypes.c_void_p),
                 ("h_bstride", ctypes.c_long), ("out2", ctypes.c_void_p), ("out2_bstride", ctypes.c_long),
                 ("in_norm", ctypes.c_void_p), ("stride", ctypes.c_int), ("stats_ws", ctypes.c_void_p),
-                ("stats_part", ctypes.c_void_p)]
+                ("stats_part", ctypes.c_void_p), ("dscale", ctypes.c_void_p)]
 
 
 class ConvC8Desc(ctypes.Structure):
@@ -236,8 +235,6 @@ SIGNATURES = {
     "dkt_gru_gate_zr_bwd": [_vp, _vp, _l, _vp, _vp, _vp, _l, _vp, _vp, _i, _i, _l, _i, _vp],
     "dkt_conv2d_packed_elems": [_ip, _i, _i, _i, _i],
     "dkt_conv2d_pack_weights": [_vp, _ip, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp],
-    "dkt_conv2d_f16s": [_pp, _ip, _lp, _i, _vp, _vp, _vp, _f, _f, _vp, _l,
-                        _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_conv_grad_prepass_ws_floats": [_i, _i, _l],
     "dkt_conv_grad_prepass": [_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _l, _i, _vp],
     "dkt_conv2d_wgrad_ws_floats": [_i, _i, _i, _i, _i, _i],
@@ -247,7 +244,6 @@ SIGNATURES = {
     "dkt_conv2d_wgrad_s2": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_conv2d_wgrad7_ws_floats": [_i, _i, _i, _i, _i],
     "dkt_conv2d_wgrad7": [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "dkt_conv2d_f16s_dscale": [_pp, _ip, _lp, _i, _vp, _vp, _f, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_instance_norm_stats": [_vp, _vp, _i, _l, _i, _vp],
     "dkt_instance_norm_add_relu": [_vp, _vp, _vp, _vp, _i, _l, _f, _i, _vp],
     "dkt_instance_norm_finalize": [_vp, _i, _l, _f, _vp, _i, _vp],
@@ -258,12 +254,6 @@ SIGNATURES = {
     "dkt_conv2d_stem7_packed_elems": [_i],
     "dkt_conv2d_stem7_pack": [_vp, _i, _i, _f, _vp, _vp, _i, _vp],
     "dkt_conv2d_stem7": [_vp, _l, _vp, _vp, _vp, _f, _f, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "dkt_conv2d_f16s_strided": [_pp, _ip, _lp, _i, _vp, _vp, _vp, _f, _f, _vp, _l,
-                                _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "dkt_conv2d_f16s_gate_zr": [_pp, _ip, _lp, _i, _vp, _vp, _vp, _f, _f, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l,
-                                _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "dkt_conv2d_f16s_gate_out": [_pp, _ip, _lp, _i, _vp, _vp, _vp, _f, _f, _vp, _l, _vp, _l, _vp, _l, _vp, _l,
-                                 _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_conv2d_direct": [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_conv2d_direct_accumulate": [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_conv2d_direct_accumulate_diff": [_vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp],

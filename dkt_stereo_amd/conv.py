@@ -6,7 +6,7 @@ reference would ``torch.cat`` along channels first (core/update.py:24-25,29,83);
 the merged z|r pair built by ``ConvGRU``).
 
 Backends (``set_backend``; default "f16x3"):
-  "f16x3"    dkt_conv2d_f16s, passes=3: fp32 emulated on the fp16 matrix cores
+  "f16x3"    dkt_conv2d_f16s_desc, passes=3: fp32 emulated on the fp16 matrix cores
              with split operands (w_hi*x_hi + w_lo*x_hi + w_hi*x_lo, fp32
              accumulate) -- ~22 bits per operand, 1.5e-6 relative to an fp64
              convolution (the vendor fp32 path: 0.9e-6); list inputs are read in
@@ -162,7 +162,7 @@ def _write_packed(p, layer, scale):
 
 
 def _packed_weights(layer, src_channels, scale=None):
-    """Split-fp16 weight image for dkt_conv2d_f16s, cached on the layer per device and operand split and rebuilt when the
+    """Split-fp16 weight image for dkt_conv2d_f16s_desc, cached on the layer per device and operand split and rebuilt when the
     parameter tensor is replaced or written.  `scale`: the power-of-two weight scale when the caller already knows it (a
     rearrangement of a packed weight), else it is read from max|w| (a host sync)."""
     w = layer.weight
@@ -270,7 +270,7 @@ def _plain_conv(layer):
 
 
 def hip_eligible(layer):
-    """True when `layer` runs on dkt_conv2d_f16s[_strided] under the current backend:
+    """True when `layer` runs on dkt_conv2d_f16s_desc under the current backend:
     1x1 / 3x3, padding K/2, stride 1 or 2, no groups / dilation."""
     kh, kw = layer.weight.shape[2:]
     pad = _padding_of(layer)
@@ -294,7 +294,7 @@ def direct_eligible(layer):
 def few_eligible(layer):
     """3x3, stride 1, padding 1, at most 4 output channels (flow_head.conv2 256 -> 2, disp_head.conv2 256 -> 1):
     an HBM-bound layer that runs on the exact-fp32 DMA-staged kernel (dkt_conv2d_direct) instead of padding its
-    outputs to a 32-channel matrix-core tile.  (`_FEW_DIRECT = False` sends it back to dkt_conv2d_f16s.)"""
+    outputs to a 32-channel matrix-core tile.  (`_FEW_DIRECT = False` sends it back to dkt_conv2d_f16s_desc.)"""
     if get_backend() not in _PASSES or not _plain_conv(layer) or not _FEW_DIRECT:
         return False
     cout, cin, kh, kw = layer.weight.shape
@@ -302,7 +302,7 @@ def few_eligible(layer):
     if not (kh == 3 and kw == 3 and pad == (1, 1) and _stride_of(layer) == (1, 1) and cout <= 4):
         return False
     # what launch_few (conv_direct.hip) can stage in 160 KB of LDS: 110592 B of patches + 384 B per (8-channel slice, output);
-    # wider layers (Cin > 1104 / 552 / 272 for 1 / 2 / 3-4 outputs) stay on dkt_conv2d_f16s
+    # wider layers (Cin > 1104 / 552 / 272 for 1 / 2 / 3-4 outputs) stay on dkt_conv2d_f16s_desc
     to = 1 if cout <= 1 else 2 if cout <= 2 else 4
     return 110592 + 384 * ((cin + 7) // 8) * to <= 160 * 1024
 
@@ -382,7 +382,7 @@ def _conv2d_stem7(x, layer, relu, out):
 
 
 class _Operands:
-    """The cat operands of one convolution marshalled for the C ABI (keeps them alive)."""
+    """The cat operands of one convolution and its packed weights (keeps them alive)."""
 
     def __init__(self, x, layer, pack_scale=None):
         srcs = list(x) if isinstance(x, (list, tuple)) else [x]
@@ -393,12 +393,8 @@ class _Operands:
         self.srcs = srcs = [s if _dense(s) else s.contiguous() for s in srcs]
         _record_range(layer, srcs)
         self.B, _, self.H, self.W = srcs[0].shape
-        chans = [int(s.shape[1]) for s in srcs]
-        self.n = n = len(srcs)
-        self.pk = _packed_weights(layer, chans, pack_scale)
-        self.ptrs = (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs])
-        self.ch = (ctypes.c_int * n)(*chans)
-        self.bs = (ctypes.c_long * n)(*[s.stride(0) for s in srcs])
+        self.n = len(srcs)
+        self.pk = _packed_weights(layer, [int(s.shape[1]) for s in srcs], pack_scale)
         self.kh, self.kw = layer.weight.shape[2:]
         self.cout = layer.weight.shape[0]
         self.bias = None if self.pk.bias is None else self.pk.bias.data_ptr()
@@ -406,13 +402,11 @@ class _Operands:
         self.in_scale = 2.0 ** in_exp_of(layer)
         self.passes = _PASSES[get_backend()]
 
-    def head(self):
-        return (self.ptrs, self.ch, self.bs, self.n, self.pk.hi.data_ptr(), self.pk.lo.data_ptr(),
-                self.bias, self.pk.inv_scale / self.in_scale, self.in_scale)
 
-
-def _desc(op, out, relu=False, epilogue=0, e0=None, e1=None, h=None, out2=None):
-    """dkt_conv_desc for one convolution of a paired launch (keeps `op` alive through the returned object)."""
+def _desc(op, out, relu=False, epilogue=0, e0=None, e1=None, h=None, out2=None, stride=0):
+    """dkt_conv_desc of one convolution, the one marshaller of every dkt_conv2d_f16s_desc / _pair launch (keeps `op` and the
+    tensors alive through the returned object; `passes` rides along for _launch).  Field by field: one constructor call with
+    every field as a keyword measured 0.6 .. 1.5 us per call slower (profiles/conv2d_one_entry.txt)."""
     d = _ffi.ConvDesc()
     for i in range(op.n):
         d.src[i] = op.srcs[i].data_ptr()
@@ -424,13 +418,78 @@ def _desc(op, out, relu=False, epilogue=0, e0=None, e1=None, h=None, out2=None):
     d.out_scale, d.in_scale = op.pk.inv_scale / op.in_scale, op.in_scale
     d.out, d.out_bstride = out.data_ptr(), out.stride(0)
     d.B, d.H, d.W, d.Cout, d.KH, d.KW, d.relu = op.B, op.H, op.W, op.cout, op.kh, op.kw, int(bool(relu))
-    d.epilogue = epilogue
-    for name, t in (("e0", e0), ("e1", e1), ("h", h), ("out2", out2)):
-        if t is not None:
-            setattr(d, name, t.data_ptr())
-            setattr(d, name + "_bstride", t.stride(0))
+    d.epilogue, d.stride = epilogue, stride
+    if e0 is not None:
+        d.e0, d.e0_bstride = e0.data_ptr(), e0.stride(0)
+    if e1 is not None:
+        d.e1, d.e1_bstride = e1.data_ptr(), e1.stride(0)
+    if h is not None:
+        d.h, d.h_bstride = h.data_ptr(), h.stride(0)
+    if out2 is not None:
+        d.out2, d.out2_bstride = out2.data_ptr(), out2.stride(0)
+    d.passes = op.passes
     d._keep = (op, out, e0, e1, h, out2)
     return d
+
+
+def _launch(descs, passes, ref):
+    """One descriptor goes to dkt_conv2d_f16s_desc, two go to dkt_conv2d_f16s_pair, on `ref`'s device and current stream."""
+    name = "dkt_conv2d_f16s_desc" if len(descs) == 1 else "dkt_conv2d_f16s_pair"
+    rc = getattr(_ffi.lib(), name)(*[ctypes.byref(d) for d in descs], passes, _ffi.device_of(ref), _ffi.stream_of(ref))
+    _ffi.check(rc, name)
+
+
+# One job builder per operation: each returns (descriptor, result) and serves the single call and its *_pair twin.
+def _plain_job(x, layer, relu=False, out=None):
+    """[relu](conv(x) + bias) at the layer's stride, into `out` when given."""
+    op = _Operands(x, layer)
+    stride = _stride_of(layer)[0]
+    shape = (op.B, op.cout, (op.H - 1) // stride + 1, (op.W - 1) // stride + 1)
+    if out is None:
+        out = torch.empty(shape, device=op.device, dtype=torch.float32)
+    elif not _dense(out) or out.dtype != torch.float32 or tuple(out.shape) != shape:
+        raise ValueError("conv2d(out=...) must be a dense-per-batch fp32 tensor of the result shape")
+    return _desc(op, out, relu=relu, stride=stride), out
+
+
+def _set_in_norm(d, in_norm):
+    """The (mean, 1/std) planes of conv2d_fused / conv2d_stats into a stride-1 descriptor."""
+    op = d._keep[0]
+    if d.stride == 2 or op.n != 1 or in_norm.dtype != torch.float32 or in_norm.numel() != 2 * op.B * int(op.srcs[0].shape[1]):
+        raise ValueError("in_norm must hold (mean, 1/std) for every (batch, channel) plane of one stride-1 operand")
+    in_norm = in_norm.contiguous()
+    d.in_norm = in_norm.data_ptr()
+    d._keep = d._keep + (in_norm,)
+
+
+def _fused_job(x, layer, relu=False, residual=None, in_norm=None):
+    """conv2d_fused: a stride-1 layer with the residual join in its epilogue and / or the input's instance norm."""
+    op = _Operands(x, layer)
+    out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
+    if residual is not None:
+        if tuple(residual.shape) != tuple(out.shape):
+            raise ValueError("conv2d_fused: residual shape %s != result shape %s" % (tuple(residual.shape), tuple(out.shape)))
+        residual = residual if _dense(residual) else residual.contiguous()
+        _ffi.require_gpu(residual)
+        _ffi.require_no_grad(residual)
+    d = _desc(op, out, relu=relu, epilogue=3 if residual is not None else 0, e0=residual)
+    if in_norm is not None:
+        _set_in_norm(d, in_norm)
+    return d, out
+
+
+def _gate_zr_job(x, zr_layer, cz, cr, h):
+    op = _Operands(x, zr_layer)
+    z = torch.empty((op.B, op.cout // 2, op.H, op.W), device=op.device, dtype=torch.float32)
+    rh = torch.empty_like(z)
+    return _desc(op, z, epilogue=1, e0=cz, e1=cr, h=h, out2=rh), (z, rh)
+
+
+def _gate_out_job(x, q_layer, cq, z, h, out=None):
+    op = _Operands(x, q_layer)
+    if out is None:
+        out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
+    return _desc(op, out, epilogue=2, e0=cq, e1=z, h=h), out
 
 
 def fused_eligible(layer, in_norm=False):
@@ -447,23 +506,8 @@ def conv2d_fused(x, layer, relu=False, residual=None, in_norm=None):
       in_norm : (B*Cin, 2) float (mean, 1/std) per input plane -> the layer reads relu((x - mean) * invstd);
       residual: tensor shaped like the result -> relu(residual + [relu](conv(x) + bias)).
     Bit-identical to the separate passes (same arithmetic, same order)."""
-    op = _Operands(x, layer)
-    out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
-    if residual is not None:
-        if tuple(residual.shape) != tuple(out.shape):
-            raise ValueError("conv2d_fused: residual shape %s != result shape %s" % (tuple(residual.shape), tuple(out.shape)))
-        residual = residual if _dense(residual) else residual.contiguous()
-        _ffi.require_gpu(residual)
-        _ffi.require_no_grad(residual)
-    d = _desc(op, out, relu=relu, epilogue=3 if residual is not None else 0, e0=residual)
-    if in_norm is not None:
-        if op.n != 1 or in_norm.dtype != torch.float32 or in_norm.numel() != 2 * op.B * int(op.srcs[0].shape[1]):
-            raise ValueError("conv2d_fused: in_norm must hold (mean, 1/std) for every (batch, channel) plane of one operand")
-        in_norm = in_norm.contiguous()
-        d.in_norm = in_norm.data_ptr()
-        d._keep = d._keep + (in_norm,)
-    rc = _ffi.lib().dkt_conv2d_f16s_desc(ctypes.byref(d), op.passes, _ffi.device_of(out), _ffi.stream_of(out))
-    _ffi.check(rc, "dkt_conv2d_f16s_desc")
+    d, out = _fused_job(x, layer, relu, residual, in_norm)
+    _launch([d], d.passes, out)
     return out
 
 
@@ -486,31 +530,20 @@ def conv2d_stats(x, layer, in_norm=None, _ws=None, relu=False):
     """conv(x) + bias [ReLU] with the statistics of its OWN output for the InstanceNorm2d that follows it
     (core/extractor.py:46-50): returns (out, OutStats).  `in_norm` as in conv2d_fused (stride 1 only).
     `_ws`: the per-(tile, wave row) scratch of dkt_conv2d_stats_ws_floats floats, handed in by the guarded-buffer test."""
-    op = _Operands(x, layer)
-    stride = _stride_of(layer)[0]
-    Ho, Wo = (op.H - 1) // stride + 1, (op.W - 1) // stride + 1
-    out = torch.empty((op.B, op.cout, Ho, Wo), device=op.device, dtype=torch.float32)
+    d, out = _plain_job(x, layer, relu)
+    B, cout, Ho, Wo = out.shape
     L = _ffi.lib()
-    d = _desc(op, out, relu=relu)
-    d.stride = stride
-    planes = op.B * op.cout
-    n_ws = int(L.dkt_conv2d_stats_ws_floats(op.B, op.cout, Ho, Wo))
-    ws = torch.empty(n_ws, device=op.device, dtype=torch.float32) if _ws is None else _ws
+    n_ws = int(L.dkt_conv2d_stats_ws_floats(B, cout, Ho, Wo))
+    ws = torch.empty(n_ws, device=out.device, dtype=torch.float32) if _ws is None else _ws
     if ws.numel() < n_ws or ws.dtype != torch.float32 or not ws.is_contiguous():
         raise ValueError("conv2d_stats: scratch of dkt_conv2d_stats_ws_floats floats expected")
-    part = torch.empty(int(L.dkt_instance_norm_workspace(planes, Ho * Wo)), device=op.device, dtype=torch.uint8)
+    part = torch.empty(int(L.dkt_instance_norm_workspace(B * cout, Ho * Wo)), device=out.device, dtype=torch.uint8)
     d.stats_ws, d.stats_part = ws.data_ptr(), part.data_ptr()
-    keep = (ws, part)
+    d._keep = d._keep + (ws, part)
     if in_norm is not None:
-        if stride != 1 or op.n != 1 or in_norm.dtype != torch.float32 or in_norm.numel() != 2 * op.B * int(op.srcs[0].shape[1]):
-            raise ValueError("conv2d_stats: in_norm must hold (mean, 1/std) for every (batch, channel) plane of one operand")
-        in_norm = in_norm.contiguous()
-        d.in_norm = in_norm.data_ptr()
-        keep = keep + (in_norm,)
-    d._keep = d._keep + keep
-    rc = L.dkt_conv2d_f16s_desc(ctypes.byref(d), op.passes, _ffi.device_of(out), _ffi.stream_of(out))
-    _ffi.check(rc, "dkt_conv2d_f16s_desc")
-    return out, OutStats(part, planes, Ho * Wo)
+        _set_in_norm(d, in_norm)
+    _launch([d], d.passes, out)
+    return out, OutStats(part, B * cout, Ho * Wo)
 
 
 def pair_eligible(layer_a, layer_b):
@@ -522,73 +555,35 @@ def pair_eligible(layer_a, layer_b):
             and wa.shape[2] == wb.shape[2] and cls(wa.shape[0]) == cls(wb.shape[0]))
 
 
-def _launch_pair(da, db, passes, ref):
-    rc = _ffi.lib().dkt_conv2d_f16s_pair(ctypes.byref(da), ctypes.byref(db), passes, _ffi.device_of(ref), _ffi.stream_of(ref))
-    _ffi.check(rc, "dkt_conv2d_f16s_pair")
-
-
 def conv2d_pair(a, b):
     """Two independent stride-1 convolutions (bias + optional ReLU) in one launch.  a, b = (x, layer, relu);
     the layers must satisfy ``pair_eligible``.  Returns (y_a, y_b)."""
-    res, descs, passes = [], [], None
-    for x, layer, relu in (a, b):
-        op = _Operands(x, layer)
-        out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
-        descs.append(_desc(op, out, relu=relu))
-        res.append(out)
-        passes = op.passes
-    _launch_pair(descs[0], descs[1], passes, res[0])
-    return res
+    (da, ya), (db, yb) = _plain_job(*a), _plain_job(*b)
+    _launch([da, db], db.passes, ya)
+    return [ya, yb]
 
 
 def conv2d_fused_pair(a, b):
     """conv2d_fused (residual epilogue) for two independent layers in one launch.  a, b = (x, layer, relu, residual);
     the layers must satisfy ``pair_eligible`` and ``fused_eligible``.  Returns (y_a, y_b)."""
-    res, descs, passes = [], [], None
-    for x, layer, relu, residual in (a, b):
-        op = _Operands(x, layer)
-        out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
-        if residual is not None:
-            if tuple(residual.shape) != tuple(out.shape):
-                raise ValueError("conv2d_fused_pair: residual shape %s != result shape %s" % (tuple(residual.shape), tuple(out.shape)))
-            residual = residual if _dense(residual) else residual.contiguous()
-            _ffi.require_gpu(residual)
-            _ffi.require_no_grad(residual)
-        descs.append(_desc(op, out, relu=relu, epilogue=3 if residual is not None else 0, e0=residual))
-        res.append(out)
-        passes = op.passes
-    _launch_pair(descs[0], descs[1], passes, res[0])
-    return res
+    (da, ya), (db, yb) = _fused_job(*a), _fused_job(*b)
+    _launch([da, db], db.passes, ya)
+    return [ya, yb]
 
 
 def conv2d_gate_zr_pair(a, b):
     """conv2d_gate_zr for two independent GRUs in one launch.  a, b = (x, zr_layer, cz, cr, h);
     returns ((z_a, rh_a), (z_b, rh_b))."""
-    res, descs, passes = [], [], None
-    for x, zr_layer, cz, cr, h in (a, b):
-        op = _Operands(x, zr_layer)
-        ch = op.cout // 2
-        z = torch.empty((op.B, ch, op.H, op.W), device=op.device, dtype=torch.float32)
-        rh = torch.empty_like(z)
-        descs.append(_desc(op, z, epilogue=1, e0=cz, e1=cr, h=h, out2=rh))
-        res.append((z, rh))
-        passes = op.passes
-    _launch_pair(descs[0], descs[1], passes, res[0][0])
-    return res
+    (da, ya), (db, yb) = _gate_zr_job(*a), _gate_zr_job(*b)
+    _launch([da, db], db.passes, ya[0])
+    return [ya, yb]
 
 
 def conv2d_gate_out_pair(a, b):
     """conv2d_gate_out for two independent GRUs in one launch.  a, b = (x, q_layer, cq, z, h, out)."""
-    res, descs, passes = [], [], None
-    for x, q_layer, cq, z, h, out in (a, b):
-        op = _Operands(x, q_layer)
-        if out is None:
-            out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
-        descs.append(_desc(op, out, epilogue=2, e0=cq, e1=z, h=h))
-        res.append(out)
-        passes = op.passes
-    _launch_pair(descs[0], descs[1], passes, res[0])
-    return res
+    (da, ya), (db, yb) = _gate_out_job(*a), _gate_out_job(*b)
+    _launch([da, db], db.passes, ya)
+    return [ya, yb]
 
 
 def conv2d(x, layer, relu=False, out=None):
@@ -606,22 +601,8 @@ def conv2d(x, layer, relu=False, out=None):
             out.copy_(y)
             return out
         return y
-    op = _Operands(x, layer)
-    stride = _stride_of(layer)[0]
-    Ho, Wo = (op.H - 1) // stride + 1, (op.W - 1) // stride + 1
-    if out is None:
-        out = torch.empty((op.B, op.cout, Ho, Wo), device=op.device, dtype=torch.float32)
-    elif not _dense(out) or out.dtype != torch.float32 or tuple(out.shape) != (op.B, op.cout, Ho, Wo):
-        raise ValueError("conv2d(out=...) must be a dense-per-batch fp32 tensor of the result shape")
-    if stride == 1:
-        rc = _ffi.lib().dkt_conv2d_f16s(*op.head(), out.data_ptr(), out.stride(0), op.B, op.H, op.W, op.cout,
-                                        op.kh, op.kw, int(bool(relu)), op.passes,
-                                        _ffi.device_of(out), _ffi.stream_of(out))
-    else:
-        rc = _ffi.lib().dkt_conv2d_f16s_strided(*op.head(), out.data_ptr(), out.stride(0), op.B, op.H, op.W, op.cout,
-                                                op.kh, op.kw, stride, int(bool(relu)), op.passes,
-                                                _ffi.device_of(out), _ffi.stream_of(out))
-    _ffi.check(rc, "dkt_conv2d_f16s")
+    d, out = _plain_job(x, layer, relu, out)
+    _launch([d], d.passes, out)
     return out
 
 
@@ -629,29 +610,16 @@ def conv2d_gate_zr(x, zr_layer, cz, cr, h):
     """ConvGRU first stage with the gates in the convolution epilogue:
     returns (z, r*h) = (sigmoid(convz(x)+cz), sigmoid(convr(x)+cr)*h); `zr_layer` is the
     merged convz|convr pair.  cz, cr, h: (B,Ch,H,W), dense per batch element."""
-    op = _Operands(x, zr_layer)
-    ch = op.cout // 2
-    z = torch.empty((op.B, ch, op.H, op.W), device=op.device, dtype=torch.float32)
-    rh = torch.empty_like(z)
-    rc = _ffi.lib().dkt_conv2d_f16s_gate_zr(*op.head(), cz.data_ptr(), cz.stride(0), cr.data_ptr(), cr.stride(0),
-                                            h.data_ptr(), h.stride(0), z.data_ptr(), z.stride(0),
-                                            rh.data_ptr(), rh.stride(0), op.B, op.H, op.W, ch, op.kh, op.kw,
-                                            op.passes, _ffi.device_of(z), _ffi.stream_of(z))
-    _ffi.check(rc, "dkt_conv2d_f16s_gate_zr")
+    d, (z, rh) = _gate_zr_job(x, zr_layer, cz, cr, h)
+    _launch([d], d.passes, z)
     return z, rh
 
 
 def conv2d_gate_out(x, q_layer, cq, z, h, out=None):
     """ConvGRU second stage: (1-z)*h + z*tanh(convq(x)+cq), written to `out` (default: new
     tensor; `out` may be `h` itself for an in-place state update)."""
-    op = _Operands(x, q_layer)
-    if out is None:
-        out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_conv2d_f16s_gate_out(*op.head(), cq.data_ptr(), cq.stride(0), z.data_ptr(), z.stride(0),
-                                             h.data_ptr(), h.stride(0), out.data_ptr(), out.stride(0),
-                                             op.B, op.H, op.W, op.cout, op.kh, op.kw,
-                                             op.passes, _ffi.device_of(out), _ffi.stream_of(out))
-    _ffi.check(rc, "dkt_conv2d_f16s_gate_out")
+    d, out = _gate_out_job(x, q_layer, cq, z, h, out)
+    _launch([d], d.passes, out)
     return out
 
 
@@ -665,7 +633,7 @@ def conv2d_gate_out(x, q_layer, cq, z, h, out=None):
 #
 # Backward with GRAD_PREPASS (default): one streaming pre-pass (dkt_conv_grad_prepass) masks the upstream gradient with the
 # saved ReLU output, sums the bias gradient in a fixed order and leaves the RANGE of the masked gradient in device memory;
-# the input-gradient convolution (dkt_conv2d_f16s_dscale) takes its activation scale from there, so a gradient of any
+# the input-gradient convolution (dkt_conv_desc.dscale) takes its activation scale from there, so a gradient of any
 # magnitude -- 1e-6 from a mean-reduced loss, 1e+6 under a loss scale -- keeps the ~22 bits of the split instead of the
 # format's absolute 2^-25 floor, and a power-of-two multiple of the upstream gradient gives that multiple of gx and gb bit
 # for bit.  The host reads nothing back.  The packed images of both orientations live on a persistent OWNER (the nn.Module,
@@ -768,7 +736,7 @@ wcache.register("_dkt_grad", _refresh_grad, derived=True)
 
 
 def _dscale_eligible(shim):
-    """The input gradient runs on dkt_conv2d_f16s_dscale: what conv2d() would send to dkt_conv2d_f16s."""
+    """The input gradient runs on the device-scaled form: what conv2d() would send to dkt_conv2d_f16s_desc."""
     return hip_eligible(shim) and not few_eligible(shim) and not direct_eligible(shim)
 
 
@@ -804,13 +772,15 @@ def conv_grad_prepass(gy, y=None, want_bias=True):
 
 def conv2d_dscale(g, layer, scale, pack_scale=None):
     """Stride-1 convolution of `g` with `layer`'s weight (no bias) whose activation scale is the device pair `scale`
-    (dkt_conv2d_f16s_dscale): in_scale = scale[0], the result is un-scaled by scale[1] in the epilogue."""
+    (dkt_conv_desc.dscale): in_scale = scale[0], the result is un-scaled by scale[1] in the epilogue."""
     op = _Operands(g, layer, pack_scale)
     out = torch.empty((op.B, op.cout, op.H, op.W), device=op.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_conv2d_f16s_dscale(op.ptrs, op.ch, op.bs, op.n, op.pk.hi.data_ptr(), op.pk.lo.data_ptr(),
-                                           op.pk.inv_scale, scale.data_ptr(), out.data_ptr(), out.stride(0), op.B, op.H,
-                                           op.W, op.cout, op.kh, op.kw, op.passes, _ffi.device_of(out), _ffi.stream_of(out))
-    _ffi.check(rc, "dkt_conv2d_f16s_dscale")
+    d = _desc(op, out)
+    d.bias = None                                    # (the input gradient has none, whatever the layer carries)
+    d.out_scale, d.in_scale = op.pk.inv_scale, 1.0
+    d.dscale = scale.data_ptr()
+    d._keep = d._keep + (scale,)
+    _launch([d], d.passes, out)
     return out
 
 

@@ -642,8 +642,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4 ? 1 : CONV_MIN_BLOCKS)) 
             }
         };
         // ---- one dispatch per tile.  What no host path launches is not instantiated: the gate kinds need stride 1 and host
-        // scales (conv_fill refuses them at stride 2, the device-scaled entry has none), kinds 1 and 2 no input norm
-        // (conv_fill_desc), and the device-scaled entry asks for no statistics.
+        // scales (conv_fill refuses them at stride 2 and beside `dscale`), kinds 1 and 2 no input norm (conv_tile_select),
+        // and conv_fill refuses statistics beside `dscale`.
         if (epi == 0) {
             const bool stats = want_stats != 0;
             if (fast) body_plain(ConvTag<1>{});
@@ -939,63 +939,73 @@ template int conv2d_launch_passes<(CONV_TU_PASSES - 1) % 3 + 1, (CONV_TU_PASSES 
 #endif
 
 #if !defined(CONV_TU_PASSES) || CONV_TU_PASSES == 0
-struct ConvEpilogue {
-    int kind;
-    const float *c0, *c1, *h;
-    long c0_bs, c1_bs, h_bs;
-    float *out2;
-    long out2_bs;
-};
-
-// validates one convolution's parameters and fills its kernel argument block
-static int conv_fill(ConvArgs &a, const float *const *src, const int *src_channels, const long *src_bstride,
-                     int nsrc, const void *w_hi, const void *w_lo, const float *bias,
-                     float out_scale, float in_scale, float *out, long out_bstride,
-                     int B, int H, int W, int Cout, int KH, int KW, int relu, int passes,
-                     const ConvEpilogue *epi, int stride) {
-    if (!src || !src_channels || !src_bstride || !w_hi || !w_lo || !out) return DKT_E_NULL;
-    const int rc = conv_query_check(stride, epi ? epi->kind : 0, nsrc, B, H, W, Cout, KH, KW, passes);
-    if (rc != DKT_OK) return rc;
-    if (!(in_scale > 0.0f) || !(out_scale > 0.0f)) return DKT_E_SHAPE;
-    for (int s = 0; s < CONV_MAX_SRC; ++s) {
-        a.src[s] = s < nsrc ? src[s] : nullptr;
-        a.src_bs[s] = s < nsrc ? src_bstride[s] : 0;
-        a.src_ch[s] = s < nsrc ? src_channels[s] : 0;
-        if (s < nsrc && (!src[s] || src_channels[s] <= 0)) return DKT_E_NULL;
+// The one validator of the launch entries: checks a descriptor and fills its kernel argument block.
+static int conv_fill(ConvArgs &a, const dkt_conv_desc *d, int passes) {
+    if (!d) return DKT_E_NULL;
+    if (d->epilogue < 0 || d->epilogue > 3) return DKT_E_UNSUPPORTED;
+    if (d->epilogue == 1) {
+        if (!d->e0 || !d->e1 || !d->h || !d->out2) return DKT_E_NULL;
+        if (d->Cout % 128 != 0) return DKT_E_UNSUPPORTED;          // Ch multiple of 64: z and r never share a wave
+    } else if (d->epilogue == 2) {
+        if (!d->e0 || !d->e1 || !d->h) return DKT_E_NULL;
+    } else if (d->epilogue == 3) {
+        if (!d->e0) return DKT_E_NULL;
     }
-    a.nsrc = nsrc;
-    a.whi = (const _Float16 *)w_hi;
-    a.wlo = (const _Float16 *)w_lo;
-    a.bias = bias;
-    a.out_scale = out_scale;
-    a.in_scale = in_scale;
-    a.out = out;
-    a.out_bs = out_bstride;
-    a.H = H; a.W = W; a.Cout = Cout;
+    if (d->stride != 0 && d->stride != 1 && d->stride != 2) return DKT_E_UNSUPPORTED;
+    const int stride = d->stride == 2 ? 2 : 1;
+    // device-resident scales: the plain stride-1 layer alone (the pair sits in the slot of in_norm)
+    if (d->dscale && (d->bias || d->relu || d->epilogue || d->in_norm || d->stats_ws || d->stats_part || stride == 2))
+        return DKT_E_UNSUPPORTED;
+    if (!d->w_hi || !d->w_lo || !d->out) return DKT_E_NULL;
+    const int rc = conv_query_check(stride, d->epilogue, d->nsrc, d->B, d->H, d->W, d->Cout, d->KH, d->KW, passes);
+    if (rc != DKT_OK) return rc;
+    if (!(d->in_scale > 0.0f) || !(d->out_scale > 0.0f)) return DKT_E_SHAPE;
+    for (int s = 0; s < CONV_MAX_SRC; ++s) {
+        a.src[s] = s < d->nsrc ? d->src[s] : nullptr;
+        a.src_bs[s] = s < d->nsrc ? d->src_bstride[s] : 0;
+        a.src_ch[s] = s < d->nsrc ? d->src_channels[s] : 0;
+        if (s < d->nsrc && (!d->src[s] || d->src_channels[s] <= 0)) return DKT_E_NULL;
+    }
+    a.nsrc = d->nsrc;
+    a.whi = (const _Float16 *)d->w_hi;
+    a.wlo = (const _Float16 *)d->w_lo;
+    a.bias = d->bias;
+    a.out_scale = d->out_scale;
+    a.in_scale = d->in_scale;
+    a.out = d->out;
+    a.out_bs = d->out_bstride;
+    a.H = d->H; a.W = d->W; a.Cout = d->Cout;
     // "same"-style padding KH/2 (what every layer on the path uses): output = floor((H - 1) / stride) + 1
-    a.Ho = (H - 1) / stride + 1;
-    a.Wo = (W - 1) / stride + 1;
-    a.CoutPad = conv_cout_pad(Cout);
-    a.nch16 = conv_padded_channels(src_channels, nsrc) / 16;
+    a.Ho = (d->H - 1) / stride + 1;
+    a.Wo = (d->W - 1) / stride + 1;
+    a.CoutPad = conv_cout_pad(d->Cout);
+    a.nch16 = conv_padded_channels(d->src_channels, d->nsrc) / 16;
     a.tiles_w = (a.Wo + 31) / 32;
     a.tiles_xy = a.n_co = a.total_tiles = 0;       // set by launch_conv (they depend on the tile shape)
-    a.relu = relu ? 1 : 0;
-    a.epi = 0;
+    a.relu = d->relu ? 1 : 0;
+    a.epi = d->epilogue;
     a.e_c0 = a.e_c1 = a.e_h = nullptr;
     a.e_c0_bs = a.e_c1_bs = a.e_h_bs = 0;
     a.out2 = nullptr;
     a.out2_bs = 0;
-    a.in_norm = nullptr;
+    if (d->epilogue) {
+        a.e_c0 = d->e0; a.e_c1 = d->e1; a.e_h = d->h;
+        a.e_c0_bs = d->e0_bstride; a.e_c1_bs = d->e1_bstride; a.e_h_bs = d->h_bstride;
+        a.out2 = d->out2; a.out2_bs = d->out2_bstride;
+    }
     a.stats_ws = nullptr;
     a.stats_part = nullptr;
     a.stats_hw = 0;
-    a.src_px = 1; a.src_w = W; a.src_hw = (long)H * W;
-    if (epi) {
-        a.epi = epi->kind;
-        a.e_c0 = epi->c0; a.e_c1 = epi->c1; a.e_h = epi->h;
-        a.e_c0_bs = epi->c0_bs; a.e_c1_bs = epi->c1_bs; a.e_h_bs = epi->h_bs;
-        a.out2 = epi->out2; a.out2_bs = epi->out2_bs;
+    a.src_px = 1; a.src_w = d->W; a.src_hw = (long)d->H * d->W;
+    if (d->stats_ws || d->stats_part) {
+        if (!d->stats_ws || !d->stats_part) return DKT_E_NULL;
+        if (d->epilogue != 0) return DKT_E_UNSUPPORTED;
+        a.stats_ws = d->stats_ws;
+        a.stats_part = (double *)d->stats_part;
     }
+    // DSC: in_scale = dscale[0], out_scale = w_inv_scale * dscale[1], both read by the kernel; else (mean, 1/std) of the
+    // in-norm form (what it supports: conv_tile_select) or nothing
+    a.in_norm = d->dscale ? d->dscale : d->in_norm;
     return DKT_OK;
 }
 
@@ -1017,48 +1027,6 @@ static int conv_run(ConvArgs &a, int B, int KH, int stride, int passes, int form
     return dsc ? conv2d_launch_passes<1, 1>(t, a, B, st, sec) : conv2d_launch_passes<1, 0>(t, a, B, st, sec);
 }
 
-static int conv2d_f16s_impl(const float *const *src, const int *src_channels, const long *src_bstride,
-                            int nsrc, const void *w_hi, const void *w_lo, const float *bias,
-                            float out_scale, float in_scale, float *out, long out_bstride,
-                            int B, int H, int W, int Cout, int KH, int KW, int relu, int passes,
-                            const ConvEpilogue *epi, int device, void *stream, int stride = 1) {
-    ConvArgs a;
-    const int rc = conv_fill(a, src, src_channels, src_bstride, nsrc, w_hi, w_lo, bias, out_scale, in_scale, out,
-                             out_bstride, B, H, W, Cout, KH, KW, relu, passes, epi, stride);
-    if (rc != DKT_OK) return rc;
-    return conv_run(a, B, KH, stride, passes, CONV_FORM_SINGLE, device, stream);
-}
-
-// ---- two convolutions in one launch (descriptor form) ----
-static int conv_fill_desc(ConvArgs &a, const dkt_conv_desc *d, int passes) {
-    if (!d) return DKT_E_NULL;
-    ConvEpilogue e = {d->epilogue, d->e0, d->e1, d->h, d->e0_bstride, d->e1_bstride, d->h_bstride, d->out2, d->out2_bstride};
-    if (d->epilogue < 0 || d->epilogue > 3) return DKT_E_UNSUPPORTED;
-    if (d->epilogue == 1) {
-        if (!d->e0 || !d->e1 || !d->h || !d->out2) return DKT_E_NULL;
-        if (d->Cout % 128 != 0) return DKT_E_UNSUPPORTED;          // Ch multiple of 64: z and r never share a wave
-    } else if (d->epilogue == 2) {
-        if (!d->e0 || !d->e1 || !d->h) return DKT_E_NULL;
-    } else if (d->epilogue == 3) {
-        if (!d->e0) return DKT_E_NULL;
-    }
-    const int stride = d->stride == 2 ? 2 : 1;
-    if (d->stride != 0 && d->stride != 1 && d->stride != 2) return DKT_E_UNSUPPORTED;
-    const int rc = conv_fill(a, d->src, d->src_channels, d->src_bstride, d->nsrc, d->w_hi, d->w_lo, d->bias, d->out_scale,
-                             d->in_scale, d->out, d->out_bstride, d->B, d->H, d->W, d->Cout, d->KH, d->KW,
-                             d->relu, passes,
-                             d->epilogue ? &e : nullptr, stride);
-    if (rc != DKT_OK) return rc;
-    if (d->stats_ws || d->stats_part) {
-        if (!d->stats_ws || !d->stats_part) return DKT_E_NULL;
-        if (d->epilogue != 0) return DKT_E_UNSUPPORTED;
-        a.stats_ws = d->stats_ws;
-        a.stats_part = (double *)d->stats_part;
-    }
-    a.in_norm = d->in_norm;         // (what the in-norm form supports: conv_tile_select)
-    return DKT_OK;
-}
-
 extern "C" long dkt_conv2d_stats_ws_floats(int B, int Cout, int Ho, int Wo) {
     if (B <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return DKT_E_SHAPE;
     // One entry per (tile, wave row): tiles_w * ceil(Ho / TR) * WN per image with TR = WN * NF rows per tile, TR in {1, 2, 4, 8}
@@ -1078,81 +1046,23 @@ extern "C" int dkt_conv2d_f16s_tile(int KS, int stride, int passes, int Cout, co
 
 extern "C" int dkt_conv2d_f16s_desc(const dkt_conv_desc *p, int passes, int device, void *stream) {
     ConvArgs a;
-    const int rc = conv_fill_desc(a, p, passes);
+    const int rc = conv_fill(a, p, passes);
     if (rc != DKT_OK) return rc;
-    return conv_run(a, p->B, p->KH, p->stride == 2 ? 2 : 1, passes, p->in_norm ? CONV_FORM_NORM : CONV_FORM_SINGLE, device, stream);
+    const int form = p->dscale ? CONV_FORM_DSCALE : p->in_norm ? CONV_FORM_NORM : CONV_FORM_SINGLE;
+    return conv_run(a, p->B, p->KH, p->stride == 2 ? 2 : 1, passes, form, device, stream);
 }
 
 extern "C" int dkt_conv2d_f16s_pair(const dkt_conv_desc *p0, const dkt_conv_desc *p1, int passes, int device, void *stream) {
     ConvArgs a;
     ConvSecond sec;
-    int rc = conv_fill_desc(a, p0, passes);
+    int rc = conv_fill(a, p0, passes);
     if (rc != DKT_OK) return rc;
-    rc = conv_fill_desc(sec.a, p1, passes);
+    rc = conv_fill(sec.a, p1, passes);
     if (rc != DKT_OK) return rc;
-    if (p0->in_norm || p1->in_norm || p0->stride == 2 || p1->stride == 2) return DKT_E_UNSUPPORTED;
+    if (p0->in_norm || p1->in_norm || p0->dscale || p1->dscale || p0->stride == 2 || p1->stride == 2) return DKT_E_UNSUPPORTED;
     sec.B = p1->B;
     // both problems run one kernel instantiation: same filter size and the same output-width class
     if (p0->KH != p1->KH || conv_width_class(p0->Cout) != conv_width_class(p1->Cout)) return DKT_E_UNSUPPORTED;
     return conv_run(a, p0->B, p0->KH, 1, passes, CONV_FORM_PAIR, device, stream, &sec);
-}
-
-extern "C" int dkt_conv2d_f16s(const float *const *src, const int *src_channels, const long *src_bstride,
-                               int nsrc, const void *w_hi, const void *w_lo, const float *bias,
-                               float out_scale, float in_scale, float *out, long out_bstride,
-                               int B, int H, int W, int Cout, int KH, int KW, int relu, int passes,
-                               int device, void *stream) {
-    return conv2d_f16s_impl(src, src_channels, src_bstride, nsrc, w_hi, w_lo, bias, out_scale, in_scale, out, out_bstride,
-                            B, H, W, Cout, KH, KW, relu, passes, nullptr, device, stream);
-}
-
-extern "C" int dkt_conv2d_f16s_dscale(const float *const *src, const int *src_channels, const long *src_bstride,
-                                      int nsrc, const void *w_hi, const void *w_lo, float w_inv_scale, const float *scale,
-                                      float *out, long out_bstride, int B, int H, int W, int Cout, int KH, int KW,
-                                      int passes, int device, void *stream) {
-    if (!scale) return DKT_E_NULL;
-    ConvArgs a;
-    const int rc = conv_fill(a, src, src_channels, src_bstride, nsrc, w_hi, w_lo, nullptr, w_inv_scale, 1.0f, out,
-                             out_bstride, B, H, W, Cout, KH, KW, 0, passes, nullptr, 1);
-    if (rc != DKT_OK) return rc;
-    a.in_norm = scale;         // DSC: in_scale = scale[0], out_scale = w_inv_scale * scale[1], both read by the kernel
-    return conv_run(a, B, KH, 1, passes, CONV_FORM_DSCALE, device, stream);
-}
-
-extern "C" int dkt_conv2d_f16s_strided(const float *const *src, const int *src_channels, const long *src_bstride,
-                                       int nsrc, const void *w_hi, const void *w_lo, const float *bias,
-                                       float out_scale, float in_scale, float *out, long out_bstride,
-                                       int B, int H, int W, int Cout, int KH, int KW, int stride, int relu,
-                                       int passes, int device, void *stream) {
-    return conv2d_f16s_impl(src, src_channels, src_bstride, nsrc, w_hi, w_lo, bias, out_scale, in_scale, out, out_bstride,
-                            B, H, W, Cout, KH, KW, relu, passes, nullptr, device, stream, stride);
-}
-
-extern "C" int dkt_conv2d_f16s_gate_zr(const float *const *src, const int *src_channels, const long *src_bstride,
-                                       int nsrc, const void *w_hi, const void *w_lo, const float *bias,
-                                       float out_scale, float in_scale, const float *cz, long cz_bstride,
-                                       const float *cr, long cr_bstride, const float *h, long h_bstride,
-                                       float *z, long z_bstride, float *rh, long rh_bstride,
-                                       int B, int H, int W, int Ch, int KH, int KW, int passes,
-                                       int device, void *stream) {
-    if (!cz || !cr || !h || !z || !rh) return DKT_E_NULL;
-    if (Ch <= 0 || Ch % 64 != 0) return DKT_E_UNSUPPORTED;   // z and r channels must not share a wave
-    ConvEpilogue e = {1, cz, cr, h, cz_bstride, cr_bstride, h_bstride, rh, rh_bstride};
-    return conv2d_f16s_impl(src, src_channels, src_bstride, nsrc, w_hi, w_lo, bias, out_scale, in_scale, z, z_bstride,
-                            B, H, W, 2 * Ch, KH, KW, 0, passes, &e, device, stream);
-}
-
-extern "C" int dkt_conv2d_f16s_gate_out(const float *const *src, const int *src_channels, const long *src_bstride,
-                                        int nsrc, const void *w_hi, const void *w_lo, const float *bias,
-                                        float out_scale, float in_scale, const float *cq, long cq_bstride,
-                                        const float *z, long z_bstride, const float *h, long h_bstride,
-                                        float *hout, long hout_bstride,
-                                        int B, int H, int W, int Ch, int KH, int KW, int passes,
-                                        int device, void *stream) {
-    if (!cq || !z || !h || !hout) return DKT_E_NULL;
-    if (Ch <= 0) return DKT_E_SHAPE;
-    ConvEpilogue e = {2, cq, z, h, cq_bstride, z_bstride, h_bstride, nullptr, 0};
-    return conv2d_f16s_impl(src, src_channels, src_bstride, nsrc, w_hi, w_lo, bias, out_scale, in_scale, hout, hout_bstride,
-                            B, H, W, Ch, KH, KW, 0, passes, &e, device, stream);
 }
 #endif  // CONV_TU_PASSES == 0 (ABI entry points)

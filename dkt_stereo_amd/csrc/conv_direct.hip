@@ -434,7 +434,7 @@ static int conv2d_direct_impl(const float *x, long x_bstride, const float *w, co
     DKT_ENTER(device);
     hipStream_t st = (hipStream_t)stream;
     if (KH == 3) {
-        if (Cout > 4) return DKT_E_UNSUPPORTED;       // wide layers belong to dkt_conv2d_f16s
+        if (Cout > 4) return DKT_E_UNSUPPORTED;       // wide layers belong to dkt_conv2d_f16s_desc
         if (Cout <= 1) return launch_few<1>(a, B, st);
         if (Cout <= 2) return launch_few<2>(a, B, st);
         return launch_few<4>(a, B, st);

@@ -4,7 +4,7 @@
 //   gb = g'.sum((0, 2, 3))       the bias gradient
 // and, for this library's split-fp16 input-gradient convolution, the RANGE of g':  a power of two 2^e that puts max|g'| in
 // [2^12, 2^13) -- the window the weights are packed in -- so that the convolution keeps ~22 bits of a gradient of any
-// magnitude (dkt_conv2d_f16s_dscale reads {2^e, 2^-e} from device memory; the host reads nothing back).
+// magnitude (dkt_conv2d_f16s_desc with `dscale` reads {2^e, 2^-e} from device memory; the host reads nothing back).
 //
 //   dkt_conv_grad_prepass   one streaming pass over gy [and y], then a one-block finish
 //

@@ -1,4 +1,4 @@
-// conv_tile.h -- the ONE place that decides which kernel and tile shape a dkt_conv2d_f16s* call runs on.  Plain C++ (no HIP,
+// conv_tile.h -- the ONE place that decides which kernel and tile shape a dkt_conv2d_f16s_desc / _pair call runs on.  Plain C++ (no HIP,
 // no kernel argument block): conv2d.hip asks conv_tile_select() before every launch and generates the launch of each shape
 // from CONV_TILE_TABLE; dkt_conv2d_f16s_tile() gives the tests the same answer.  A tile shape is tuned here and nowhere else.
 // Wave tile = 32*MF output channels x NF rows x 32 columns; WM x WN waves along (channels, rows); ST the stride; activations
@@ -41,7 +41,7 @@ struct ConvTile { int kernel, KS, WM, WN, NF, MF, ST, CK; };
 // (H, W the INPUT size; form: one problem, the first of a pair launch, in-norm input, device-resident scales)
 struct ConvTileQuery { int KS, stride, passes, Cout, nsrc; const int *src_channels; int epilogue, B, H, W, form; };
 
-// What every form asks of a call's integers (the entry points check pointers and scales themselves).
+// What every form asks of a call's integers (conv_fill checks pointers, scales and the options of the descriptor).
 static inline int conv_query_check(int stride, int epilogue, int nsrc, int B, int H, int W, int Cout, int KH, int KW, int passes) {
     if (stride != 1 && (stride != 2 || epilogue)) return DKT_E_UNSUPPORTED;
     if (nsrc < 1 || nsrc > DKT_CONV_MAX_SRC || B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || B > 65535) return DKT_E_SHAPE;

@@ -4,7 +4,7 @@ They run once per pair and produce the feature maps and GRU context the hot path
 published checkpoints must load, so parameter names follow the reference's
 ``core/extractor.py`` (``BasicEncoder`` :122-197, ``MultiBasicEncoder`` :199-300,
 ``ResidualBlock`` :6-60).  On a HIP device in inference every convolution runs on this
-library's kernels (1x1 / 3x3 with stride 1 or 2: dkt_conv2d_f16s[_strided]; the 7x7 stem:
+library's kernels (1x1 / 3x3 with stride 1 or 2: dkt_conv2d_f16s_desc; the 7x7 stem:
 dkt_conv2d_stem7), eval-mode BatchNorm is folded into the convolution, instance norm and the
 residual join are streaming kernels; anything else (training, CPU, group norm) is plain torch.
 """
@@ -48,7 +48,7 @@ TRAIN_NORM_NODES = False
 
 
 #: the encoders' convolutions under autograd (trainable weights or an input that requires grad) as conv.conv2d_autograd
-#: nodes -- forward on this library's kernels, backward on the pre-pass, dkt_conv2d_f16s_dscale / dkt_conv2d_wgrad and, for
+#: nodes -- forward on this library's kernels, backward on the pre-pass, the device-scaled dkt_conv2d_f16s_desc / dkt_conv2d_wgrad and, for
 #: the down-sampling layers, dkt_conv2d_dgrad_s2 / dkt_conv2d_wgrad_s2 -- instead of nn.Conv2d (A/B handle).
 #: The rule of 3.15: on only once tools/bench_encoder_train.py has shown its arm ahead of arm a by more than the a-to-a
 #: spread at both training shapes.

@@ -13,7 +13,7 @@ nodes (backward: volumes_bwd.hip); the 2-D and 3-D layers are torch with batch-s
 
 What runs where (inference, ``test_mode=True``):
   * 2-D feature extraction: every 3x3 / 1x1 convolution with its eval-mode BatchNorm folded in runs on
-    dkt_conv2d_f16s[_strided]; the dilated layer4 stays on the vendor library;
+    dkt_conv2d_f16s_desc; the dilated layer4 stays on the vendor library;
   * group-wise correlation (40 groups) + concatenation volume: ONE 64-channel buffer written by
     dkt_gwc_volume / dkt_concat_volume (the reference's torch.cat of a 250 MB and a 150 MB tensor,
     gwc_main.py:315, never happens);

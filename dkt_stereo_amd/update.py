@@ -12,7 +12,7 @@ published checkpoints load with ``strict=True``:
 What differs from the reference is how a GRU step is evaluated (core/update.py:23-32):
   * convz and convr run as ONE convolution with concatenated output channels;
   * default path: the gate arithmetic lives in the convolution epilogues
-    (dkt_conv2d_f16s_gate_zr / _gate_out): two launches per GRU, no z|r / q pre-activation
+    (dkt_conv2d_f16s_desc, epilogues 1 and 2): two launches per GRU, no z|r / q pre-activation
     tensors, and the reference's torch.cat operands are read in place;
   * FUSE_GATES = False or the vendor-convolution backend: two streaming gate kernels
     (dkt_gru_gate_zr / _out) after the convolutions instead of ~12 elementwise launches.
@@ -145,7 +145,7 @@ def harness(**switches):
             setattr(_HARNESS, k, v)
 
 
-#: evaluate the GRU gates inside the convolution epilogues (dkt_conv2d_f16s_gate_zr/_out)
+#: evaluate the GRU gates inside the convolution epilogues (conv.conv2d_gate_zr / conv2d_gate_out)
 #: instead of the two streaming gate kernels
 FUSE_GATES = True
 

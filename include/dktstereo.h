@@ -395,39 +395,20 @@ int dkt_gru_gate_zr_bwd(const float *gz, const float *grh, long grh_bstride, con
  *   out[b,co,h,w] = [relu]( bias[co] + sum_k weight[co,k] * lookup[b,k,h,w] )
  * tap (optional, may be NULL): receives lookup[b,k,h,w] itself -- bit-identical to dkt_corr1d_lookup_skew.
  * Supported: Cout <= 64, L in {2,3,4}, r in {3,4}; otherwise DKT_E_UNSUPPORTED (callers then run
- * dkt_corr1d_lookup_skew + dkt_conv2d_f16s). */
+ * dkt_corr1d_lookup_skew + dkt_conv2d_f16s_desc). */
 int dkt_corr1d_lookup_conv1x1(const float *const *skew, const float *coords_x, long coords_bstride,
                               const float *weight_t, const float *bias, float *out, long out_bstride,
                               float *tap, long tap_bstride,
                               int B, int H, int W1, int W2, int L, int r, int Cout, int relu,
                               int device, void *stream);
 
-/* nn.Conv2d (stride 1, "same" zero padding, 1x1 or 3x3) as used by ConvGRU,
- * BasicMotionEncoder, FlowHead/DispHead and the mask heads (core/update.py:9-10,
- * 19-21, 72-76, 111-113; meta_arch/igev_stereo/update.py same lines), evaluated
- * as an implicit GEMM on the fp16 matrix cores with split operands and fp32
- * accumulation (see conv2d.hip).  `src` are up to DKT_CONV_MAX_SRC NCHW fp32
- * tensors that the reference concatenates along channels before the
- * convolution (torch.cat at core/update.py:24-25,29,83) -- they are read in
- * place.  passes: 3 = w_hi*x_hi + w_lo*x_hi + w_hi*x_lo (fp32-class accuracy),
- * 2 = activations rounded to fp16, 1 = plain fp16.
- *   out[b,co,h,w] = out_scale * acc + bias[co], optional ReLU; (B,Cout,H,W) with
- *   batch stride out_bstride.
- * The weights must have been packed by dkt_conv2d_pack_weights with the SAME
- * src_channels list.  Activations are multiplied by in_scale (a power of two, 1 by default in the
- * Python layer) before they are split into fp16 parts; out_scale = 1 / (weight scale * in_scale).
- * Range: |x * in_scale| < 65520; 22 significant bits for |x * in_scale| >= 2^-3, an absolute
- * floor of 2^-25 below.  Out-of-range, Inf and NaN activations yield non-finite outputs (they are
- * never saturated silently). */
+/* Weight images of the split-fp16 convolution (dkt_conv2d_f16s_desc / _pair below, where the contract is): packed once per
+ * layer, for one list of cat operands. */
 #define DKT_CONV_MAX_SRC 4
 long dkt_conv2d_packed_elems(const int *src_channels, int nsrc, int Cout, int KH, int KW);
 int dkt_conv2d_pack_weights(const float *w /* (Cout,sum(src_channels),KH,KW) */,
                             const int *src_channels, int nsrc, int Cout, int KH, int KW, float scale,
                             void *w_hi /* fp16[packed_elems] */, void *w_lo, int device, void *stream);
-int dkt_conv2d_f16s(const float *const *src, const int *src_channels, const long *src_bstride, int nsrc,
-                    const void *w_hi, const void *w_lo, const float *bias, float out_scale, float in_scale,
-                    float *out, long out_bstride, int B, int H, int W, int Cout, int KH, int KW,
-                    int relu, int passes, int device, void *stream);
 
 /* ---- backward of the update-operator convolutions (training; dkt_stereo_amd/conv.py: _Conv2dFn.backward) ----
  * torch autograd through [relu](conv2d(x, w, b)), stride 1, "same" padding (core/update.py:9-10, 19-21, 72-76, 111-113):
@@ -442,7 +423,7 @@ int dkt_conv2d_f16s(const float *const *src, const int *src_channels, const long
  *          for the 16-byte and the 4-byte path alike.
  *   scale  two floats {2^e, 2^-e}: e = 12 - floor(log2(max|g'|)), i.e. max|g'| * 2^e in [2^12, 2^13) (the window
  *          dkt_conv2d_pack_weights' callers put the weights in), clamped to |e| <= DKT_CONV_GRAD_MAX_EXP, which keeps both
- *          floats, and out_scale of dkt_conv2d_f16s_dscale for any weight scale in [2^-46, 2^46], normal; e = 0 when
+ *          floats, and the out_scale of a dkt_conv_desc with `dscale` for any weight scale in [2^-46, 2^46], normal; e = 0 when
  *          max|g'| is 0, Inf or NaN (a non-finite gradient is passed on as it is and comes out non-finite).
  *   ws     dkt_conv_grad_prepass_ws_floats(B, C, HW) floats of scratch, written before they are read.
  * 16-byte accesses when HW, the batch strides and the pointers allow it, 4-byte ones otherwise.
@@ -527,51 +508,43 @@ int dkt_conv2d_wgrad7(const float *x, long x_bstride, const float *g, long g_bst
                       float *gw /* (Cout,Cin,7,7) dense */, float *ws,
                       int B, int Cin, int Cout, int H, int W, int device, void *stream);
 
-/* dkt_conv2d_f16s (stride 1, no bias, no ReLU, no epilogue) with the activation scale in DEVICE memory: the input-gradient
- * convolution, whose operand range only the device knows.  scale = {s, 1/s} as dkt_conv_grad_prepass writes it:
- *   in_scale = scale[0],  out_scale = w_inv_scale * scale[1]   (w_inv_scale: 1 / the weight scale of the pack),
- * read by the kernel; a gradient of any magnitude keeps the ~22 bits of the split, and a power-of-two multiple of the
- * operand gives that multiple of the result bit for bit.  Errors as dkt_conv2d_f16s, scale null DKT_E_NULL. */
-int dkt_conv2d_f16s_dscale(const float *const *src, const int *src_channels, const long *src_bstride, int nsrc,
-                           const void *w_hi, const void *w_lo, float w_inv_scale, const float *scale,
-                           float *out, long out_bstride, int B, int H, int W, int Cout, int KH, int KW,
-                           int passes, int device, void *stream);
-
-/* dkt_conv2d_f16s with a stride (1 or 2) and padding K/2: the down-sampling convolutions of the
- * encoders (core/extractor.py:16,34: 3x3 stride 2 and the 1x1 stride-2 projection).  H, W are the
- * INPUT size; out is (B, Cout, (H-1)/stride+1, (W-1)/stride+1). */
-int dkt_conv2d_f16s_strided(const float *const *src, const int *src_channels, const long *src_bstride,
-                            int nsrc, const void *w_hi, const void *w_lo, const float *bias,
-                            float out_scale, float in_scale, float *out, long out_bstride,
-                            int B, int H, int W, int Cout, int KH, int KW, int stride, int relu,
-                            int passes, int device, void *stream);
-
-/* ConvGRU with the gate arithmetic fused into the convolution epilogues (core/update.py:23-32):
- * no z|r / q pre-activation tensors ever reach HBM.
- *   gate_zr : merged convz|convr over [h | x...] (2*Ch outputs, packed as one layer):
- *             z = sigmoid(conv_z + cz) -> z;  rh = sigmoid(conv_r + cr) * h -> rh
- *   gate_out: convq over [rh | x...]:  hout = (1 - z)*h + z*tanh(conv_q + cq)   (hout may alias h)
- * Ch must be a multiple of 64 for gate_zr.  Same arithmetic as dkt_gru_gate_zr/_out. */
-int dkt_conv2d_f16s_gate_zr(const float *const *src, const int *src_channels, const long *src_bstride, int nsrc,
-                            const void *w_hi, const void *w_lo, const float *bias, float out_scale, float in_scale,
-                            const float *cz, long cz_bstride, const float *cr, long cr_bstride,
-                            const float *h, long h_bstride, float *z, long z_bstride, float *rh, long rh_bstride,
-                            int B, int H, int W, int Ch, int KH, int KW, int passes, int device, void *stream);
-int dkt_conv2d_f16s_gate_out(const float *const *src, const int *src_channels, const long *src_bstride, int nsrc,
-                             const void *w_hi, const void *w_lo, const float *bias, float out_scale, float in_scale,
-                             const float *cq, long cq_bstride, const float *z, long z_bstride,
-                             const float *h, long h_bstride, float *hout, long hout_bstride,
-                             int B, int H, int W, int Ch, int KH, int KW, int passes, int device, void *stream);
-
-/* Two independent convolutions of dkt_conv2d_f16s' kind (stride 1, optional ConvGRU gate epilogue) in ONE
+/* nn.Conv2d with "same" zero padding K/2, 1x1 or 3x3, stride 1 or 2, as used by ConvGRU, BasicMotionEncoder,
+ * FlowHead/DispHead, the mask heads (core/update.py:9-10, 19-21, 72-76, 111-113; meta_arch/igev_stereo/update.py same
+ * lines) and the encoders (core/extractor.py:16,34), evaluated as an implicit GEMM on the fp16 matrix cores with split
+ * operands and fp32 accumulation (see conv2d.hip).  One convolution is one dkt_conv_desc; a zero-initialised descriptor
+ * leaves every option off.
+ *   src       up to DKT_CONV_MAX_SRC NCHW fp32 tensors that the reference concatenates along channels before the
+ *             convolution (torch.cat at core/update.py:24-25,29,83) -- they are read in place.  The weights must have been
+ *             packed by dkt_conv2d_pack_weights with the SAME src_channels list.
+ *   passes    (an argument of the launch) 3 = w_hi*x_hi + w_lo*x_hi + w_hi*x_lo (fp32-class accuracy), 2 = activations
+ *             rounded to fp16, 1 = plain fp16.
+ *   scales    activations are multiplied by in_scale (a power of two, 1 by default in the Python layer) before they are
+ *             split into fp16 parts; out_scale = 1 / (weight scale * in_scale).  Range: |x * in_scale| < 65520; 22
+ *             significant bits for |x * in_scale| >= 2^-3, an absolute floor of 2^-25 below.  Out-of-range, Inf and NaN
+ *             activations yield non-finite outputs (they are never saturated silently).
+ *   stride    H, W are the INPUT size; out is (B, Cout, (H-1)/stride+1, (W-1)/stride+1) with batch stride out_bstride.
+ *             Stride 2 (the encoders' 3x3 down-sampling layers and 1x1 projections) takes epilogue 0 only.
+ *   epilogue 0: out[b,co,h,w] = out_scale*acc + bias[co] [ReLU];  Cout = layer outputs
+ *   epilogue 1: ConvGRU first stage (core/update.py:23-32), the merged convz|convr layer over [h | x...], Cout = 2*Ch with
+ *               Ch a multiple of 64: z = sigmoid(conv_z + cz) -> out, r*h = sigmoid(conv_r + cr) * h -> out2
+ *               (e0 = cz, e1 = cr)
+ *   epilogue 2: ConvGRU second stage, convq over [r*h | x...], Cout = Ch: (1-z)*h + z*tanh(conv_q + cq) -> out
+ *               (e0 = cq, e1 = z; out may alias h)
+ *   epilogue 3: residual join of a residual block whose norm is folded into the weights (core/extractor.py:52-60):
+ *               out = relu(e0 + [ReLU](out_scale*acc + bias)), e0 shaped like out
+ *   With epilogues 1 and 2 no z|r / q pre-activation tensor reaches HBM; same arithmetic as dkt_gru_gate_zr/_out.
+ *   in_norm, stats_ws / stats_part, dscale: see the fields.
+ * Errors, before any device is touched: a null descriptor, w_hi, w_lo, out, source or operand of the epilogue, or a source
+ * with src_channels <= 0, DKT_E_NULL; nsrc outside 1..DKT_CONV_MAX_SRC, B, H, W or Cout <= 0, B > 65535, or a scale that
+ * is not > 0 DKT_E_SHAPE; KH != KW, KH not in {1, 3}, passes outside 1..3, an epilogue outside 0..3, a stride outside
+ * {0, 1, 2}, or a combination of options named above or at a field as unsupported DKT_E_UNSUPPORTED.
+ *
+ * dkt_conv2d_f16s_pair: two independent stride-1 convolutions (epilogues 0..3, no in_norm / stats / dscale) in ONE
  * launch: the resident blocks of the persistent kernel are split between the two problems in proportion to
  * their work.  Used to fold the coarsest GRU of iteration i+1 (36 tiles at 1/16 KITTI) into the launches of
  * the finest GRU of iteration i (core/update.py:118-127; the two are independent), where it fits in the
  * tile-quantisation slack.  Both problems must have the same KH and fall in the same output-width class
- * (<= 32, <= 64, <= 128, wider), else DKT_E_UNSUPPORTED.
- *   epilogue 0: out = out_scale*acc + bias [ReLU];  Cout = layer outputs
- *   epilogue 1: merged z|r layer, Cout = 2*Ch: z -> out, r*h -> out2 (e0 = cz, e1 = cr)
- *   epilogue 2: q layer, Cout = Ch: (1-z)*h + z*tanh(v + cq) -> out (e0 = cq, e1 = z; out may alias h) */
+ * (<= 32, <= 64, <= 128, wider), else DKT_E_UNSUPPORTED. */
 typedef struct dkt_conv_desc {
     const float *src[DKT_CONV_MAX_SRC];
     long src_bstride[DKT_CONV_MAX_SRC];
@@ -591,26 +564,29 @@ typedef struct dkt_conv_desc {
     const float *in_norm;   /* optional, dkt_conv2d_f16s_desc only: (B*src_channels[0], 2) = (mean, 1/std) per input
                              * plane; the layer convolves relu((x - mean) * invstd) instead of x (nsrc = 1, 3x3,
                              * 32 < Cout <= 128).  NULL: plain input. */
-    int stride;             /* dkt_conv2d_f16s_desc only: 0 / 1 = stride 1, 2 = stride 2 (as dkt_conv2d_f16s_strided) */
+    int stride;             /* 0 / 1 = stride 1; 2 = stride 2, dkt_conv2d_f16s_desc only */
     float *stats_ws;        /* optional, dkt_conv2d_f16s_desc with epilogue 0: scratch of dkt_conv2d_stats_ws_floats floats; */
     void *stats_part;       /* ... the instance-norm statistics of the OUTPUT (InstanceNorm2d of core/extractor.py:21-33 over
                              * this layer's result) are accumulated in the epilogue and left in stats_part, a
                              * dkt_instance_norm_workspace(B*Cout, Ho*Wo) buffer in the format dkt_instance_norm_stats writes
                              * (dkt_instance_norm_finalize / _add_relu read it): the statistics pass disappears */
+    const float *dscale;    /* optional, dkt_conv2d_f16s_desc only: the activation scale in DEVICE memory -- the input-gradient
+                             * convolution, whose operand range only the device knows.  {s, 1/s} as dkt_conv_grad_prepass
+                             * writes it: the kernel reads in_scale = dscale[0] and multiplies out_scale, here w_inv_scale =
+                             * 1 / the weight scale of the pack, by dscale[1] (the field in_scale is not read, but must be
+                             * > 0).  A gradient of any magnitude keeps the ~22 bits of the split, and a power-of-two
+                             * multiple of the operand gives that multiple of the result bit for bit.  Stride 1, epilogue 0,
+                             * no bias, ReLU, in_norm or statistics: DKT_E_UNSUPPORTED with any of them. */
 } dkt_conv_desc;
 long dkt_conv2d_stats_ws_floats(int B, int Cout, int Ho, int Wo);
 int dkt_conv2d_f16s_pair(const dkt_conv_desc *p0, const dkt_conv_desc *p1, int passes, int device, void *stream);
-/* One stride-1 convolution given as a descriptor.  Besides the epilogues above:
- *   epilogue 3: residual join of a residual block whose norm is folded into the weights
- *               (core/extractor.py:52-60): out = relu(e0 + [ReLU](out_scale*acc + bias)), e0 shaped like out;
- *   in_norm   : see the field. */
 int dkt_conv2d_f16s_desc(const dkt_conv_desc *p, int passes, int device, void *stream);
 
-/* Which kernel and tile shape a dkt_conv2d_f16s* call of these sizes runs on (core/update.py:9-10, 19-21, 72-76, 111-113;
+/* Which kernel and tile shape a dkt_conv2d_f16s_desc / _pair call of these sizes runs on (core/update.py:9-10, 19-21, 72-76, 111-113;
  * core/extractor.py:16,34): the answer of the function every launch asks (csrc/conv_tile.h), for the tests -- no device is
  * touched and no tensor pointer read.  KS the filter size (1 or 3), stride 1 or 2, H, W the INPUT size, epilogue as in
  * dkt_conv_desc, form: 0 = one problem, 1 = the first problem of dkt_conv2d_f16s_pair, 2 = with in_norm,
- * 3 = dkt_conv2d_f16s_dscale.  DKT_CONV_WS is read per call, as by a launch.
+ * 3 = descriptor with `dscale`.  DKT_CONV_WS is read per call, as by a launch.
  *   tile[8] = {kernel (0 = conv2d_f16s_kernel, 1 = the weights-stationary 64 -> 64 kernel), KS, WM, WN, NF, MF, ST, CK}:
  *   WM x WN waves along (channels, rows), each 32*MF channels x NF rows x 32 columns, stride ST, 16*CK-channel chunks.  KS
  *   and ST are what the kernel runs at: a 1x1 stride-2 layer reports ST = 1 (a stride-1 layer on a sub-sampled source).
@@ -622,7 +598,7 @@ int dkt_conv2d_f16s_tile(int KS, int stride, int passes, int Cout, const int *sr
  * core/extractor.py:136) on the fp16 matrix cores with split operands (stem7.hip): K laid out
  * over (dy, dx, ci) instead of 32-channel chunks.  Weights are pre-packed once per layer
  * (dkt_conv2d_stem7_pack, `scale` a power of two as for dkt_conv2d_pack_weights);
- * out = conv * out_scale + bias [ReLU].  Same fp32-class accuracy as dkt_conv2d_f16s(passes=3). */
+ * out = conv * out_scale + bias [ReLU].  Same fp32-class accuracy as dkt_conv2d_f16s_desc(passes = 3). */
 long dkt_conv2d_stem7_packed_elems(int Cout);
 int dkt_conv2d_stem7_pack(const float *w, int Cout, int Cin, float scale, void *w_hi, void *w_lo,
                           int device, void *stream);
@@ -755,7 +731,7 @@ int dkt_adamw_step(float *const *p, const float *const *g, float *const *exp_avg
                    float *record, float *absmax, void *workspace, int grid, int device, void *stream);
 
 /* ---- round 3: the 3x3 convolution on pre-split activations ("C8S" layout, conv_c8.hip) -------------------------
- * Same operator and arithmetic as dkt_conv2d_f16s(passes = 3) -- core/update.py:19-21,27-31 (ConvGRU), :72-76,84
+ * Same operator and arithmetic as dkt_conv2d_f16s_desc(passes = 3) -- core/update.py:19-21,27-31 (ConvGRU), :72-76,84
  * (motion encoder), :9 (FlowHead.conv1) -- but the activation operands arrive as fp16 (hi, lo) pairs written by the
  * producing kernel, so that both operands reach LDS by DMA.
  *

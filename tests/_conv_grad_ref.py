@@ -1,4 +1,4 @@
-"""Reference for the backward of conv.conv2d_autograd (csrc/conv_grad.hip, dkt_conv2d_f16s_dscale): fp64 truth for the masked
+"""Reference for the backward of conv.conv2d_autograd (csrc/conv_grad.hip, dkt_conv_desc.dscale): fp64 truth for the masked
 gradient g', the bias gradient gb and the input gradient gx from the SAME fp32 inputs the node sees (the upstream gradient,
 the saved ReLU output, the weight), a CPU emulation of the split-fp16 convolution (hi / lo fp16 of x * s, three products,
 summed in fp64), the exponent rule of the pre-pass, the fixed cases and the bounds.

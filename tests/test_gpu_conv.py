@@ -1,4 +1,4 @@
-"""-m gpu: the split-fp16 implicit-GEMM convolution (dkt_conv2d_f16s) against an fp64
+"""-m gpu: the split-fp16 implicit-GEMM convolution (dkt_conv2d_f16s_desc) against an fp64
 reference of nn.Conv2d, alone and inside the update operator / the full
 RAFT-Stereo loop.  Tolerances, relative to max|y|:
    passes=3 (w_hi*x_hi + w_lo*x_hi + w_hi*x_lo):  2e-6   (fp32-class)
@@ -126,7 +126,7 @@ def test_stem7_vs_fp64(shape):
                          ids=lambda s: s[0])
 @torch.no_grad()
 def test_strided_conv_vs_fp64(shape):
-    """dkt_conv2d_f16s_strided (stride 2, padding K/2): the encoders' down-sampling convolutions
+    """dkt_conv2d_f16s_desc at stride 2 (padding K/2): the encoders' down-sampling convolutions
     (core/extractor.py:16,34), incl. odd sizes and ReLU, against an fp64 convolution."""
     from dkt_stereo_amd import conv
     name, B, cin, cout, H, W, k = shape

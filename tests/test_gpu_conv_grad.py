@@ -1,5 +1,5 @@
 """The backward of conv.conv2d_autograd (-m gpu): the pre-pass (csrc/conv_grad.hip), the device-scaled input-gradient
-convolution (dkt_conv2d_f16s_dscale) and the owner-held packed images, against the fp64 truth and the bounds of
+convolution (dkt_conv_desc.dscale) and the owner-held packed images, against the fp64 truth and the bounds of
 _conv_grad_ref.py at upstream gradients of magnitude 2^0, 2^-20, 2^-40 and 2^+20.
 
 Every case prints its figures (run with -s).  Host synchronisations are looked for with

@@ -103,7 +103,7 @@ def _check_multi(label, m, x, norm, ds, nl, n_heads, dual=False, begun=False, ke
 
 
 def _assert_vendor_stem(m):
-    """downsample = 3: the 7x7 stride-2 stem is outside dkt_conv2d_stem7 (stride 1) and dkt_conv2d_f16s (1x1 / 3x3) and goes to
+    """downsample = 3: the 7x7 stride-2 stem is outside dkt_conv2d_stem7 (stride 1) and dkt_conv2d_f16s_desc (1x1 / 3x3) and goes to
     the vendor convolution by design (conv.conv2d); it is compared with the truth like every other layer."""
     from dkt_stereo_amd import conv
     assert m.conv1.stride == (2, 2) and not conv.direct_eligible(m.conv1) and not conv.hip_eligible(m.conv1)

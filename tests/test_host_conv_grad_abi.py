@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-NAMES = ["dkt_conv_grad_prepass_ws_floats", "dkt_conv_grad_prepass", "dkt_conv2d_f16s_dscale"]
+NAMES = ["dkt_conv_grad_prepass_ws_floats", "dkt_conv_grad_prepass"]
 _CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}
 
 
@@ -32,6 +32,42 @@ def _declared(name):
     return m.group(1), args
 
 
+def _declared_struct(name):
+    """[(field, ctype)] of `typedef struct name { ... } name;` as include/dktstereo.h declares it: pointers as c_void_p,
+    arrays by the header's own #define of their length."""
+    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    consts = {k: int(v) for k, v in re.findall(r"#define\s+(\w+)\s+(\d+)\s*$", hdr, flags=re.M)}
+    m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), hdr, flags=re.S)
+    assert m, name
+    fields = []
+    for decl in m.group(1).split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        base = re.match(r"(?:const )?(void|float|int|long)\b", decl)
+        assert base, decl
+        for item in decl[base.end():].split(","):
+            star, field, dim = re.match(r"\s*(\*?)\s*(\w+)(?:\[(\w+)\])?\s*$", item).groups()
+            ct = ctypes.c_void_p if star else _CTYPES[base.group(1)]
+            fields.append((field, ct * (consts[dim] if dim in consts else int(dim)) if dim else ct))
+    return fields
+
+
+def test_conv_desc_mirrors_the_header():
+    """_ffi.ConvDesc is dkt_conv_desc field for field -- names, order, array lengths, C types: every dkt_conv2d_f16s launch
+    goes through that mirror."""
+    from dkt_stereo_amd import _ffi
+    want = _declared_struct("dkt_conv_desc")
+    got = list(_ffi.ConvDesc._fields_)
+    assert [n for n, _ in got] == [n for n, _ in want]
+
+    def shape(t):
+        return (t._type_, t._length_) if issubclass(t, ctypes.Array) else (t, 0)
+    assert [shape(t) for _, t in got] == [shape(t) for _, t in want]
+    assert want[-1] == ("dscale", ctypes.c_void_p) and shape(want[0][1]) == (ctypes.c_void_p, 4)
+
+
 def test_signatures_match_the_header():
     from dkt_stereo_amd import _ffi
     lib = _ffi.lib()
@@ -50,7 +86,7 @@ def test_entries_refuse_bad_arguments_before_launch():
     null = ctypes.c_void_p(0)
     buf = (ctypes.c_float * 256)()
     p = ctypes.c_void_p(ctypes.addressof(buf))
-    ws, pre, conv = (getattr(lib, n) for n in NAMES)
+    ws, pre = (getattr(lib, n) for n in NAMES)
     # the workspace: 2 floats per (batch, channel, 4096-element segment)
     assert ws(2, 3, 5000) == 2 * 2 * 3 * 2 and ws(1, 1, 1) == 2 and ws(1, 1, 4096) == 2 and ws(1, 1, 4097) == 4
     for bad in ((0, 1, 1), (1, 0, 1), (1, 1, 0), (-1, 1, 1)):
@@ -65,18 +101,84 @@ def test_entries_refuse_bad_arguments_before_launch():
         assert pre(p, 8, null, 0, null, null, p, p, *bad, -1, null) == -2, bad
     assert pre(p, 7, null, 0, null, null, p, p, *tail) == -2            # a batch stride shorter than C*HW
     assert pre(p, 8, p, 7, p, null, p, p, *tail) == -2
-    # dkt_conv2d_f16s_dscale(src, ch, bs, nsrc, w_hi, w_lo, w_inv_scale, scale, out, out_bs, B, H, W, Cout, KH, KW, passes, ...)
-    src = (ctypes.c_void_p * 1)(p.value)
-    ch = (ctypes.c_int * 1)(2)
-    bs = (ctypes.c_long * 1)(8)
-    good = [src, ch, bs, 1, p, p, 1.0, p, p, 8, 1, 2, 2, 2, 3, 3, 3]
-    for k in (4, 5, 7, 8):
-        assert conv(*[null if i == k else a for i, a in enumerate(good)], -1, null) == -1, k
-    assert conv(ctypes.cast(null, ctypes.POINTER(ctypes.c_void_p)), *good[1:], -1, null) == -1
-    for i, v, want in ((10, 0, -2), (11, 0, -2), (13, -1, -2), (3, 5, -2), (6, 0.0, -2), (14, 5, -7), (15, 1, -7), (16, 4, -7)):
-        args = list(good)
-        args[i] = v
-        assert conv(*args, -1, null) == want, (i, v)
+    assert all(v == 0.0 for v in buf)                                   # nothing was written
+
+
+def _conv_desc(p, **fields):
+    """A dkt_conv_desc nothing is wrong with (2 -> 2 channels, 3x3, B = 1, 2 x 2 pixels, every tensor at `p`) but for `fields`;
+    src / src_channels set the first operand's."""
+    from dkt_stereo_amd import _ffi
+    d = _ffi.ConvDesc()
+    d.src[0], d.src_bstride[0], d.src_channels[0], d.nsrc = p, 8, 2, 1
+    d.w_hi = d.w_lo = d.out = p
+    d.out_scale = d.in_scale = 1.0
+    d.out_bstride = 8
+    d.B, d.H, d.W, d.Cout, d.KH, d.KW = 1, 2, 2, 2, 3, 3
+    for k, v in fields.items():
+        if k in ("src", "src_channels"):
+            getattr(d, k)[0] = v
+        else:
+            setattr(d, k, v)
+    return d
+
+
+def test_conv_desc_refuses_bad_arguments_before_launch():
+    """dkt_conv2d_f16s_desc / _pair, the one validator of the split-fp16 convolution.  The codes of a descriptor that says what
+    a positional entry of the parent commit said (dkt_conv2d_f16s, _strided, _gate_zr, _gate_out, _dscale) are the codes that
+    entry gave to the same arguments, taken from the parent's library (profiles/conv2d_one_entry.txt)."""
+    from dkt_stereo_amd import _ffi
+    lib = _ffi.lib()
+    buf = (ctypes.c_float * 256)()
+    p = ctypes.addressof(buf)
+
+    def run(passes=3, **fields):
+        return lib.dkt_conv2d_f16s_desc(ctypes.byref(_conv_desc(p, **fields)), passes, -1, None)
+
+    assert lib.dkt_conv2d_f16s_desc(None, 3, -1, None) == -1
+    # the device-scaled form: what dkt_conv2d_f16s_dscale refused (out_scale carries w_inv_scale)
+    for k in ("w_hi", "w_lo", "out", "src"):
+        assert run(dscale=p, **{k: None}) == -1, k
+    for k, v, want in (("B", 0, -2), ("H", 0, -2), ("Cout", -1, -2), ("nsrc", 5, -2), ("out_scale", 0.0, -2), ("KH", 5, -7),
+                       ("KW", 1, -7)):
+        assert run(dscale=p, **{k: v}) == want, (k, v)
+    assert run(passes=4, dscale=p) == -7
+    # ... and what it had no argument for
+    gate = dict(e0=p, e1=p, h=p, out2=p)
+    for extra in (dict(bias=p), dict(relu=1), dict(in_norm=p), dict(stats_ws=p, stats_part=p), dict(stats_ws=p), dict(stats_part=p),
+                  dict(stride=2), dict(epilogue=1, Cout=128, **gate), dict(epilogue=2, **gate), dict(epilogue=3, e0=p)):
+        assert run(dscale=p, **extra) == -7, extra
+    assert run(dscale=p, in_scale=0.0) == -2
+    # the plain and strided forms (dkt_conv2d_f16s, dkt_conv2d_f16s_strided)
+    for k in ("w_hi", "w_lo", "out", "src"):
+        assert run(**{k: None}) == -1, k
+    for k, v, want in (("B", 0, -2), ("H", 0, -2), ("W", 0, -2), ("Cout", 0, -2), ("Cout", -1, -2), ("nsrc", 0, -2), ("nsrc", 5, -2),
+                       ("B", 65536, -2), ("out_scale", 0.0, -2), ("in_scale", 0.0, -2), ("src_channels", 0, -1), ("KH", 5, -7),
+                       ("KW", 1, -7), ("stride", 3, -7), ("stride", -1, -7), ("epilogue", 4, -7), ("epilogue", -1, -7)):
+        assert run(**{k: v}) == want, (k, v)
+    assert run(passes=4) == -7 and run(passes=0) == -7
+    assert run(stride=2, B=0) == -2 and run(stride=2, KH=5) == -7
+    # epilogue 1 (dkt_conv2d_f16s_gate_zr: Cout = 2 * Ch, Ch a multiple of 64) and epilogue 2 (dkt_conv2d_f16s_gate_out)
+    for k in ("e0", "e1", "h", "out2"):
+        assert run(epilogue=1, Cout=128, **dict(gate, **{k: None})) == -1, k
+    for cout in (192, 64, 2):
+        assert run(epilogue=1, Cout=cout, **gate) == -7, cout
+    for k in ("e0", "e1", "h"):
+        assert run(epilogue=2, **dict(gate, **{k: None})) == -1, k
+    assert run(epilogue=2, Cout=0, **gate) == -2 and run(epilogue=3) == -1
+    for epi in (1, 2, 3):
+        assert run(epilogue=epi, Cout=128, stride=2, **gate) == -7, epi
+    for epi in (1, 2, 3):
+        assert run(epilogue=epi, Cout=128, stats_ws=p, stats_part=p, **gate) == -7, epi
+    assert run(stats_ws=p) == -1 and run(stats_part=p) == -1
+    # the pair launch: either descriptor is checked the same way, and neither may carry dscale, in_norm or stride 2
+    good = _conv_desc(p)
+    pair = lib.dkt_conv2d_f16s_pair
+    for bad, want in ((_conv_desc(p, dscale=p), -7), (_conv_desc(p, dscale=p, bias=p), -7), (_conv_desc(p, in_norm=p), -7),
+                      (_conv_desc(p, stride=2), -7), (_conv_desc(p, KH=1, KW=1), -7), (_conv_desc(p, Cout=33), -7),
+                      (_conv_desc(p, out=None), -1), (_conv_desc(p, H=0), -2)):
+        assert pair(ctypes.byref(bad), ctypes.byref(good), 3, -1, None) == want
+        assert pair(ctypes.byref(good), ctypes.byref(bad), 3, -1, None) == want
+    assert pair(None, ctypes.byref(good), 3, -1, None) == -1 and pair(ctypes.byref(good), None, 3, -1, None) == -1
     assert all(v == 0.0 for v in buf)                                   # nothing was written
 
 

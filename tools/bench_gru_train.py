@@ -8,7 +8,7 @@ updates and masks; the weights are trainable (their gradient is the vendor libra
          the nodes);
   arm b  TRAIN_NODES = True: gru_train.gate_zr / gate_out / pool2x / interp (dkt_gru_gate_*_train, dkt_gru_gate_*_bwd,
          dkt_pool2x_bwd, dkt_interp_bilinear_bwd), the convolutions' backward as before conv.GRAD_PREPASS;
-  arm c  arm b with conv.GRAD_PREPASS = True: dkt_conv_grad_prepass + dkt_conv2d_f16s_dscale, packed images held by their
+  arm c  arm b with conv.GRAD_PREPASS = True: dkt_conv_grad_prepass + the device-scaled dkt_conv2d_f16s_desc, packed images held by their
          owners, conv.GRAD_WEIGHT_HIP = False: the weight gradient on the vendor library (on a tree without the handles arm b
          is that tree's only backward);
   arm d  arm c with conv.GRAD_WEIGHT_HIP = True: dkt_conv2d_wgrad for the 1x1 and 3x3 layers (the default).
