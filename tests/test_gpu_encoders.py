@@ -8,7 +8,8 @@ Bound, per output tensor, metric max|got - truth| / max|truth|:
 where the yardstick is the same restatement in fp32 on the CPU (the error of the reference's own arithmetic on this very
 input; the fp64 truth is evaluated with the same stock operators on the device, which is several times faster); a case is valid only if its yardstick is <= 1e-5 (asserted here, proven for the fixed cases without a GPU by
 test_host_encoder_ref.py).  Where 8 and 2.9e-7 come from: _encoder_ref's docstring.  f16x2, f16 and args.mixed_precision
-are not parity paths and are not tested here.
+are not parity paths and are not tested here: the reduced-pass convolutions are held to the fp64 convolution of their rounded
+operands, operator by operator, in tests/test_gpu_conv2d_reduced_passes.py (conv2d_f16s) and tests/test_gpu_round5.py (conv_c8).
 
 Every comparison prints `ENC <case> <tensor> err yardstick ratio` before it asserts.
 

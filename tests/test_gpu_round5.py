@@ -18,6 +18,7 @@ import torch
 
 import _cases
 import _synth
+from _conv2d_ref import w_hi as _w_hi          # (the packed image's hi plane, back at w's scale)
 from test_gpu_parity import DEV, G, _raft, maxabs
 
 pytestmark = pytest.mark.gpu
@@ -182,13 +183,6 @@ def test_bench_two_ranks_over_gloo_on_one_device(tmp_path):
 # ---- reduced-pass convolutions (dkt_conv_c8_desc.passes / dkt_gru_c8_desc.passes): the arithmetic they are DEFINED to be -----------
 def _f16r(x):
     return x.half().float()
-
-
-def _w_hi(w):
-    """What the packed image's hi plane holds: fp16 of w * 2^e (max |w * 2^e| in [2^12, 2^13)), back at w's scale."""
-    import math
-    e = 12 - math.floor(math.log2(float(w.abs().max())))
-    return (w * 2.0 ** e).half().float() * 2.0 ** -e
 
 
 @torch.no_grad()
