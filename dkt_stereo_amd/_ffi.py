@@ -205,6 +205,8 @@ SIGNATURES = {
     "dkt_soft_argmin_fwd": [_vp, _l, _f, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_soft_argmin_bwd": [_vp, _l, _vp, _l, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_soft_argmin_bwd_workspace": [_i, _i, _i, _i, _i],
+    "dkt_topk_regress_fwd": [_vp, _l, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
+    "dkt_topk_regress_bwd": [_vp, _l, _vp, _l, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_corr1d_lookup_bwd": [_vp, _vp, _l, _pp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_geo_lookup_bwd": [_vp, _vp, _vp, _pp, _pp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_geo_pool_bwd": [_pp, _vp, _l, _i, _l, _i, _i, _vp],

@@ -272,6 +272,10 @@ def context_upsample(disp_low, up_weights):
     return _upsample.context_upsample_weights(disp_low, up_weights, _needs_autograd(disp_low, up_weights))
 
 
+#: meta_arch/cgi/submodule.py:220-228, one launch (topk_regress.hip); disparity_samples may be None for "the plane index"
+from .topk import regression_topk  # noqa: E402,F401
+
+
 def disparity_regression(x, maxdisp):
     """igev_stereo/submodule.py:220-224 (keepdim=True flavour)."""
     assert len(x.shape) == 4

@@ -208,6 +208,35 @@ int dkt_soft_argmin_bwd(const float *gout, long gout_bstride, const float *cost,
  * other two entries return for these sizes. */
 long dkt_soft_argmin_bwd_workspace(int B, int Dc, int h, int w, int factor);
 
+/* ---- top-k disparity regression --------------------------------------------------------- */
+
+/* CGI-Stereo's disparity head, regression_topk(cost, disparity_samples, k) (meta_arch/cgi/submodule.py:220-228: cost.sort(1,
+ * True), the first k indices, torch.gather of the cost and of the samples, F.softmax over the k, product and sum; called with
+ * k = 2 on an arange repeated to (B,D,h,w) at meta_arch/cgi/CGI_Stereo.py:256-259) in one launch, nothing sorted or gathered
+ * in memory.  cost, samples (B,D,h,w): batch strides cost_bstride, samples_bstride elements, the other dimensions contiguous;
+ * out (B,1,h,w) contiguous.  With d_0 .. d_k-1 the planes of the pixel's k largest costs, largest first (equal values in
+ * ascending plane order -- the selection of a stable descending sort, and the reference's wherever the k-th and (k+1)-th
+ * values differ; a NaN ranks above every number, as in torch's sort), c_i = cost[b,d_i,y,x] and s_i = samples[b,d_i,y,x], or
+ * (float)d_i when samples is null (the form CGI calls: no samples tensor is read or needed):
+ *   e_i = exp(c_i - c_0),  p_i = e_i / (e_0 + ... + e_k-1),  out[b,0,y,x] = s_0 p_0 + ... + s_k-1 p_k-1.
+ * A pixel whose column holds a NaN yields NaN; no other pixel is affected.  idx, when not null: (B,k,h,w) bytes,
+ * idx[b,i,y,x] = d_i -- what the backward needs of the forward.
+ * Errors (both entries): a null pointer the call needs, or gsamples without samples, DKT_E_NULL; B, D, h, w <= 0, k < 1, k > D
+ * or a batch stride shorter than one image DKT_E_SHAPE; k > 8, D > 256, B > 65535 or h*w > 2^31 - 257 DKT_E_UNSUPPORTED; a
+ * float pointer that is not a multiple of 4 bytes DKT_E_ALIGN. */
+int dkt_topk_regress_fwd(const float *cost, long cost_bstride, const float *samples /* may be null */, long samples_bstride,
+                         float *out, unsigned char *idx /* may be null */, int B, int D, int h, int w, int k,
+                         int device, void *stream);
+
+/* Its backward (torch autograd through the lines above), p_i and pred = out recomputed from cost, samples and the forward's
+ * idx: gcost[b,d_i,y,x] = gout p_i (s_i - pred), gsamples[b,d_i,y,x] = gout p_i, every other plane of both zero.  gout
+ * (B,1,h,w): batch stride gout_bstride elements; gcost, gsamples (B,D,h,w) contiguous, each written in full exactly once (no
+ * memset needed) or skipped when null (at least one is given).  One launch, deterministic: one owner per pixel, no atomics. */
+int dkt_topk_regress_bwd(const float *gout, long gout_bstride, const float *cost, long cost_bstride,
+                         const float *samples /* may be null */, long samples_bstride, const unsigned char *idx,
+                         float *gcost /* may be null */, float *gsamples /* may be null */,
+                         int B, int D, int h, int w, int k, int device, void *stream);
+
 /* ---- backward of lookup / pyramid (autograd of core/corr.py:119-146) -------- */
 
 /* Gradient of every pyramid level from the gradient of one lookup's output:
