@@ -3,7 +3,10 @@
 This is the whole Python<->native boundary of the package: device pointers come
 from ``tensor.data_ptr()``, the stream from ``torch.cuda.current_stream()``; no
 torch type crosses the ABI.  There is no CPU fallback -- if the library is
-missing or a call fails this module raises.
+missing or a call fails this module raises.  The package's modules reach the
+library through two functions only: call() for the launching entries, size()
+for the host-side size queries.  tests/test_host_abi_mirror.py compares every
+signature, structure and constant below with the header.
 """
 import ctypes
 import threading
@@ -308,7 +311,7 @@ _LAUNCH_LOG = threading.local()
 
 
 class launch_log:
-    """Collects the names of the C-ABI launches this thread makes inside the block (every launch is followed by check()):
+    """Collects the names of the C-ABI launches this thread makes inside the block (the package launches through call(); a direct lib() call is followed by check()):
     how the tests and bench.py count the dispatches of a captured loop unit."""
 
     def __enter__(self):
@@ -329,6 +332,30 @@ def check(rc, what):
     names = getattr(_LAUNCH_LOG, "names", None)
     if names is not None:
         names.append(what)
+
+
+def call(name, on, *args, ok=(), log=None):
+    """Launches entry ``name`` with ``args`` and then the device and the current stream of tensor ``on`` (every launching
+    entry ends ``int device, void *stream``), and check()s the status under ``log or name``.  A non-zero status listed
+    in ``ok`` is returned to the caller instead, unlogged: how a call site reads a refusal such as E_UNSUPPORTED."""
+    rc = getattr(_lib or lib(), name)(*args, device_of(on), stream_of(on))
+    if rc == 0:                         # (check()'s success path in place: every eager launch of the package comes through here)
+        names = getattr(_LAUNCH_LOG, "names", None)
+        if names is not None:
+            names.append(log or name)
+        return 0
+    if rc in ok:
+        return rc
+    check(rc, log or name)
+
+
+def size(name, *dims):
+    """The result of a host-only size query (*_ws_floats, *_workspace, *_packed_elems, ...) as an int; a negative one is
+    a DKT_E_* code and raises as check() words it."""
+    n = getattr(lib(), name)(*dims)
+    if n < 0:
+        check(n, name)
+    return int(n)
 
 
 def ptr(t):

@@ -153,9 +153,7 @@ def _write_packed(p, layer, scale):
     ch = (ctypes.c_int * n)(*p.src_channels)
     cout, _, kh, kw = w.shape
     wc = w.detach().float().contiguous()
-    rc = _ffi.lib().dkt_conv2d_pack_weights(wc.data_ptr(), ch, n, cout, kh, kw, scale, p.hi.data_ptr(), p.lo.data_ptr(),
-                                            _ffi.device_of(w), _ffi.stream_of(w))
-    _ffi.check(rc, "dkt_conv2d_pack_weights")
+    _ffi.call("dkt_conv2d_pack_weights", w, wc.data_ptr(), ch, n, cout, kh, kw, scale, p.hi.data_ptr(), p.lo.data_ptr())
     p.inv_scale = 1.0 / scale
     if p.bias is not None:
         _copy_unaliased(p.bias, layer.bias)
@@ -177,8 +175,8 @@ def _packed_weights(layer, src_channels, scale=None):
         if cin != sum(src_channels):
             raise ValueError("conv operands carry %d channels, layer expects %d" % (sum(src_channels), cin))
         n = len(src_channels)
-        elems = _ffi.lib().dkt_conv2d_packed_elems((ctypes.c_int * n)(*src_channels), n, cout, kh, kw)
-        if elems <= 0:
+        elems = _ffi.size("dkt_conv2d_packed_elems", (ctypes.c_int * n)(*src_channels), n, cout, kh, kw)
+        if elems == 0:
             raise _ffi.DktError("dkt_conv2d_packed_elems rejected the layer shape")
         if scale is None:
             scale = pack_scale(float(w.detach().abs().max()))
@@ -203,9 +201,7 @@ def _write_stem7(pk, layer, scale):
     """The 7x7 stem image of `layer`'s weight at `scale` into pk's buffers, the bias into pk.bias."""
     w = layer.weight
     wc = w.detach().float().contiguous()
-    rc = _ffi.lib().dkt_conv2d_stem7_pack(wc.data_ptr(), w.shape[0], w.shape[1], scale, pk.hi.data_ptr(), pk.lo.data_ptr(),
-                                          _ffi.device_of(w), _ffi.stream_of(w))
-    _ffi.check(rc, "dkt_conv2d_stem7_pack")
+    _ffi.call("dkt_conv2d_stem7_pack", w, wc.data_ptr(), w.shape[0], w.shape[1], scale, pk.hi.data_ptr(), pk.lo.data_ptr())
     pk.inv_scale = 1.0 / scale
     if pk.bias is not None:
         _copy_unaliased(pk.bias, layer.bias)
@@ -220,7 +216,7 @@ def stem7_packed(layer):
         pk = wcache.lookup(layer, "_dkt_stem7", slot, key)
         if pk is None:
             scale = pack_scale(float(w.detach().abs().max()))
-            pk = _new_packed(key, w, layer.bias, _ffi.lib().dkt_conv2d_stem7_packed_elems(w.shape[0]))
+            pk = _new_packed(key, w, layer.bias, _ffi.size("dkt_conv2d_stem7_packed_elems", w.shape[0]))
             _write_stem7(pk, layer, scale)
             wcache.store(layer, "_dkt_stem7", slot, pk)
     return pk
@@ -319,10 +315,8 @@ def _conv2d_direct(x, layer, relu, out):
     w = layer.weight.detach()
     w = w if w.is_contiguous() else w.contiguous()
     b = layer.bias
-    rc = _ffi.lib().dkt_conv2d_direct(x.data_ptr(), x.stride(0), w.data_ptr(), None if b is None else b.data_ptr(),
-                                      out.data_ptr(), out.stride(0), B, cin, cout, H, W, kh, kw, int(bool(relu)),
-                                      _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_direct")
+    _ffi.call("dkt_conv2d_direct", x, x.data_ptr(), x.stride(0), w.data_ptr(), None if b is None else b.data_ptr(),
+              out.data_ptr(), out.stride(0), B, cin, cout, H, W, kh, kw, int(bool(relu)))
     return out
 
 
@@ -347,16 +341,13 @@ def conv2d_accumulate(x, layer, out, diff=None):
         for t in (ref, dst):
             if not _dense(t) or t.dtype != torch.float32 or tuple(t.shape) != (B, cout, H, W):
                 raise ValueError("conv2d_accumulate(diff=(ref, dst)): both must be dense-per-batch fp32 tensors shaped like out")
-        rc = _ffi.lib().dkt_conv2d_direct_accumulate_diff(
+        _ffi.call(
+            "dkt_conv2d_direct_accumulate_diff", x,
             x.data_ptr(), x.stride(0), w.data_ptr(), None if b is None else b.data_ptr(), out.data_ptr(), out.stride(0),
-            ref.data_ptr(), ref.stride(0), dst.data_ptr(), dst.stride(0), B, cin, cout, H, W, kh, kw,
-            _ffi.device_of(x), _ffi.stream_of(x))
-        _ffi.check(rc, "dkt_conv2d_direct_accumulate_diff")
+            ref.data_ptr(), ref.stride(0), dst.data_ptr(), dst.stride(0), B, cin, cout, H, W, kh, kw)
         return out
-    rc = _ffi.lib().dkt_conv2d_direct_accumulate(x.data_ptr(), x.stride(0), w.data_ptr(), None if b is None else b.data_ptr(),
-                                                 out.data_ptr(), out.stride(0), B, cin, cout, H, W, kh, kw,
-                                                 _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_direct_accumulate")
+    _ffi.call("dkt_conv2d_direct_accumulate", x, x.data_ptr(), x.stride(0), w.data_ptr(), None if b is None else b.data_ptr(),
+              out.data_ptr(), out.stride(0), B, cin, cout, H, W, kh, kw)
     return out
 
 
@@ -373,11 +364,9 @@ def _conv2d_stem7(x, layer, relu, out):
     in_scale = 2.0 ** in_exp_of(layer)
     if out is None:
         out = torch.empty((B, cout, H, W), device=x.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_conv2d_stem7(x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
-                                     None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
-                                     out.data_ptr(), out.stride(0), B, cin, cout, H, W, int(bool(relu)),
-                                     _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_stem7")
+    _ffi.call("dkt_conv2d_stem7", x, x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
+              None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
+              out.data_ptr(), out.stride(0), B, cin, cout, H, W, int(bool(relu)))
     return out
 
 
@@ -435,8 +424,7 @@ def _desc(op, out, relu=False, epilogue=0, e0=None, e1=None, h=None, out2=None, 
 def _launch(descs, passes, ref):
     """One descriptor goes to dkt_conv2d_f16s_desc, two go to dkt_conv2d_f16s_pair, on `ref`'s device and current stream."""
     name = "dkt_conv2d_f16s_desc" if len(descs) == 1 else "dkt_conv2d_f16s_pair"
-    rc = getattr(_ffi.lib(), name)(*[ctypes.byref(d) for d in descs], passes, _ffi.device_of(ref), _ffi.stream_of(ref))
-    _ffi.check(rc, name)
+    _ffi.call(name, ref, *[ctypes.byref(d) for d in descs], passes)
 
 
 # One job builder per operation: each returns (descriptor, result) and serves the single call and its *_pair twin.
@@ -532,12 +520,11 @@ def conv2d_stats(x, layer, in_norm=None, _ws=None, relu=False):
     `_ws`: the per-(tile, wave row) scratch of dkt_conv2d_stats_ws_floats floats, handed in by the guarded-buffer test."""
     d, out = _plain_job(x, layer, relu)
     B, cout, Ho, Wo = out.shape
-    L = _ffi.lib()
-    n_ws = int(L.dkt_conv2d_stats_ws_floats(B, cout, Ho, Wo))
+    n_ws = _ffi.size("dkt_conv2d_stats_ws_floats", B, cout, Ho, Wo)
     ws = torch.empty(n_ws, device=out.device, dtype=torch.float32) if _ws is None else _ws
     if ws.numel() < n_ws or ws.dtype != torch.float32 or not ws.is_contiguous():
         raise ValueError("conv2d_stats: scratch of dkt_conv2d_stats_ws_floats floats expected")
-    part = torch.empty(int(L.dkt_instance_norm_workspace(B * cout, Ho * Wo)), device=out.device, dtype=torch.uint8)
+    part = torch.empty(_ffi.size("dkt_instance_norm_workspace", B * cout, Ho * Wo), device=out.device, dtype=torch.uint8)
     d.stats_ws, d.stats_part = ws.data_ptr(), part.data_ptr()
     d._keep = d._keep + (ws, part)
     if in_norm is not None:
@@ -757,16 +744,13 @@ def conv_grad_prepass(gy, y=None, want_bias=True):
     B, C, H, W = gy.shape
     gy = _dense_per_batch(gy)
     y = None if y is None else _dense_per_batch(y)
-    L = _ffi.lib()
     gm = None if y is None else torch.empty((B, C, H, W), device=gy.device, dtype=torch.float32)
     gb = torch.empty(C, device=gy.device, dtype=torch.float32) if want_bias else None
     scale = torch.empty(2, device=gy.device, dtype=torch.float32)
-    ws = torch.empty(int(L.dkt_conv_grad_prepass_ws_floats(B, C, H * W)), device=gy.device, dtype=torch.float32)
-    rc = L.dkt_conv_grad_prepass(gy.data_ptr(), _batch_stride(gy), None if y is None else y.data_ptr(),
-                                 0 if y is None else _batch_stride(y), None if gm is None else gm.data_ptr(),
-                                 None if gb is None else gb.data_ptr(), scale.data_ptr(), ws.data_ptr(), B, C, H * W,
-                                 _ffi.device_of(gy), _ffi.stream_of(gy))
-    _ffi.check(rc, "dkt_conv_grad_prepass")
+    ws = torch.empty(_ffi.size("dkt_conv_grad_prepass_ws_floats", B, C, H * W), device=gy.device, dtype=torch.float32)
+    _ffi.call("dkt_conv_grad_prepass", gy, gy.data_ptr(), _batch_stride(gy), None if y is None else y.data_ptr(),
+              0 if y is None else _batch_stride(y), None if gm is None else gm.data_ptr(),
+              None if gb is None else gb.data_ptr(), scale.data_ptr(), ws.data_ptr(), B, C, H * W)
     return (gy if gm is None else gm), gb, scale
 
 
@@ -814,15 +798,11 @@ def conv2d_wgrad(x, g, scale, k, x_scale=1.0, stride=1):
     if stride == 2 and tuple(g.shape) != (B, cout, *_out_size_s2(H, W)):
         raise ValueError("conv2d_wgrad_s2: g %s is not the stride-2 gradient of x %s" % (tuple(g.shape), tuple(x.shape)))
     x, g = _dense_per_batch(x), _dense_per_batch(g)
-    L = _ffi.lib()
-    n = int(getattr(L, name + "_ws_floats")(B, cin, cout, H, W, k))
-    if n < 0:
-        _ffi.check(n, name + "_ws_floats")
+    n = _ffi.size(name + "_ws_floats", B, cin, cout, H, W, k)
     gw = torch.empty((cout, cin, k, k), device=x.device, dtype=torch.float32)
     ws = torch.empty(n, device=x.device, dtype=torch.float32)
-    rc = getattr(L, name)(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(), float(x_scale),
-                          gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, k, _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, name)
+    _ffi.call(name, x, x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(), float(x_scale),
+              gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, k)
     return gw
 
 
@@ -850,15 +830,11 @@ def conv2d_wgrad7(x, g, scale, x_scale=1.0):
     if tuple(g.shape) != (B, cout, H, W):
         raise ValueError("conv2d_wgrad7: g %s does not match x %s" % (tuple(g.shape), tuple(x.shape)))
     x, g = _dense_per_batch(x), _dense_per_batch(g)
-    L = _ffi.lib()
-    n = int(L.dkt_conv2d_wgrad7_ws_floats(B, cin, cout, H, W))
-    if n < 0:
-        _ffi.check(n, "dkt_conv2d_wgrad7_ws_floats")
+    n = _ffi.size("dkt_conv2d_wgrad7_ws_floats", B, cin, cout, H, W)
     gw = torch.empty((cout, cin, 7, 7), device=x.device, dtype=torch.float32)
     ws = torch.empty(n, device=x.device, dtype=torch.float32)
-    rc = L.dkt_conv2d_wgrad7(x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(), float(x_scale),
-                             gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_wgrad7")
+    _ffi.call("dkt_conv2d_wgrad7", x, x.data_ptr(), _batch_stride(x), g.data_ptr(), _batch_stride(g), scale.data_ptr(),
+              float(x_scale), gw.data_ptr(), ws.data_ptr(), B, cin, cout, H, W)
     return gw
 
 
@@ -893,10 +869,8 @@ def conv2d_dgrad_s2(g, layer, scale, hw, pack_scale=None, out=None):
         raise ValueError("conv2d_dgrad_s2(out=...) must be a dense-per-batch fp32 tensor of the input's shape")
     else:
         gx = out
-    rc = _ffi.lib().dkt_conv2d_dgrad_s2(g.data_ptr(), _batch_stride(g), pk.hi.data_ptr(), pk.lo.data_ptr(), pk.inv_scale,
-                                        scale.data_ptr(), gx.data_ptr(), _batch_stride(gx), B, cin, cout, H, W, k,
-                                        _ffi.device_of(g), _ffi.stream_of(g))
-    _ffi.check(rc, "dkt_conv2d_dgrad_s2")
+    _ffi.call("dkt_conv2d_dgrad_s2", g, g.data_ptr(), _batch_stride(g), pk.hi.data_ptr(), pk.lo.data_ptr(), pk.inv_scale,
+              scale.data_ptr(), gx.data_ptr(), _batch_stride(gx), B, cin, cout, H, W, k)
     return gx
 
 

@@ -84,9 +84,7 @@ def pack(x, dst=None, ch0=0, scale=None):
         dst = ActC8(B, C, H, W, x.device, 1.0 if scale is None else scale)
     _check_dst("conv_c8.pack", dst, B, C, H, W, ch0)
     x = x if (x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W) else x.contiguous()
-    rc = _ffi.lib().dkt_act_c8_pack(x.data_ptr(), x.stride(0), dst.data_ptr(), dst.bstride_bytes, B, C, H, W, ch0,
-                                    dst.scale, _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_act_c8_pack")
+    _ffi.call("dkt_act_c8_pack", x, x.data_ptr(), x.stride(0), dst.data_ptr(), dst.bstride_bytes, B, C, H, W, ch0, dst.scale)
     return dst
 
 
@@ -94,9 +92,7 @@ def unpack(a, C=None, ch0=0):
     """Channels [ch0, ch0 + C) of an ActC8 -> fp32 NCHW, every channel decoded with its own scale (`channel_scales`)."""
     C = a.C - ch0 if C is None else C
     y = torch.empty((a.B, C, a.H, a.W), device=a.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_act_c8_unpack(a.data_ptr(), a.bstride_bytes, y.data_ptr(), y.stride(0), a.B, C, a.H, a.W, ch0,
-                                      a.scale, _ffi.device_of(y), _ffi.stream_of(y))
-    _ffi.check(rc, "dkt_act_c8_unpack")
+    _ffi.call("dkt_act_c8_unpack", y, a.data_ptr(), a.bstride_bytes, y.data_ptr(), y.stride(0), a.B, C, a.H, a.W, ch0, a.scale)
     t0 = a.C - a.tail - ch0                  # first tail channel of y
     if a.tail and a.tail_scale != a.scale and t0 < C:
         y[:, max(t0, 0):] *= a.scale / a.tail_scale          # (the kernel divided by a.scale; powers of two: exact)
@@ -187,8 +183,8 @@ def _pack_raw(w, src_channels):
     if tuple(w.shape[2:]) != (3, 3) or cin != sum(src_channels):
         raise ValueError("conv_c8: 3x3 layers only, operands carry %d channels, layer expects %d" % (sum(src_channels), cin))
     n = len(src_channels)
-    nbytes = _ffi.lib().dkt_conv_c8_packed_bytes((ctypes.c_int * n)(*src_channels), n, cout)
-    if nbytes <= 0:
+    nbytes = _ffi.size("dkt_conv_c8_packed_bytes", (ctypes.c_int * n)(*src_channels), n, cout)
+    if nbytes == 0:
         raise _ffi.DktError("dkt_conv_c8_packed_bytes rejected the layer shape")
     inv_scale = 1.0 / pack_scale(float(w.abs().max()))
     img = torch.zeros(nbytes // 2, device=w.device, dtype=torch.float16)
@@ -201,9 +197,7 @@ def _repack_raw(w, src_channels, inv_scale, img):
     n = len(src_channels)
     ch = (ctypes.c_int * n)(*src_channels)
     wc = w.float().contiguous()
-    rc = _ffi.lib().dkt_conv_c8_pack_weights(wc.data_ptr(), ch, n, int(w.shape[0]), 1.0 / inv_scale, img.data_ptr(),
-                                             _ffi.device_of(w), _ffi.stream_of(w))
-    _ffi.check(rc, "dkt_conv_c8_pack_weights")
+    _ffi.call("dkt_conv_c8_pack_weights", w, wc.data_ptr(), ch, n, int(w.shape[0]), 1.0 / inv_scale, img.data_ptr())
 
 
 def _refresh_packed_c8(layer, cache, R):
@@ -280,7 +274,7 @@ wcache.register("_dkt_gru_c8", _refresh_gru_c8, pinned=True)
 
 def gru_flags(B, H, W, device):
     """The per-tile flag words of dkt_gru_c8 for one (operator, shape) pair (zero-initialised; every launch increments them)."""
-    return torch.zeros(int(_ffi.lib().dkt_gru_c8_flag_words(B, H, W)), device=device, dtype=torch.int32)
+    return torch.zeros(_ffi.size("dkt_gru_c8_flag_words", B, H, W), device=device, dtype=torch.int32)
 
 
 def gru_desc(gru, h_c8, xs, rh_c8, cz, cr, cq, h, flags):
@@ -321,18 +315,13 @@ def gru_launch(d0, d1=None, err=None, ref=None):
     """One launch for one ConvGRU step (d1: a second, independent one riding in the same launch).  Returns False when the
     device cannot run this shape in one launch (the caller falls back to gate_zr + gate_out)."""
     ref = d0._keep[7] if ref is None else ref
-    L = _ffi.lib()
     e = None if err is None else err.data_ptr()
-    if d1 is not None:
-        d0.passes = d1.passes = max(d0.passes, d1.passes)          # (one instantiation runs both problems)
     if d1 is None:
-        rc = L.dkt_gru_c8(ctypes.byref(d0), e, _ffi.device_of(ref), _ffi.stream_of(ref))
-    else:
-        rc = L.dkt_gru_c8_pair(ctypes.byref(d0), ctypes.byref(d1), e, _ffi.device_of(ref), _ffi.stream_of(ref))
-    if rc == _ffi.E_UNSUPPORTED:
-        return False
-    _ffi.check(rc, "dkt_gru_c8")
-    return True
+        return _ffi.call("dkt_gru_c8", ref, ctypes.byref(d0), e, ok=(_ffi.E_UNSUPPORTED,)) == 0
+    d0.passes = d1.passes = max(d0.passes, d1.passes)          # (one instantiation runs both problems)
+    # logged as one ConvGRU launch: test_gpu_round5.UNIT_LAUNCHES counts the pair under the single entry's name
+    return _ffi.call("dkt_gru_c8_pair", ref, ctypes.byref(d0), ctypes.byref(d1), e, ok=(_ffi.E_UNSUPPORTED,),
+                     log="dkt_gru_c8") == 0
 
 
 def to_c4(x):
@@ -403,14 +392,12 @@ def desc(srcs, layer, relu=False, out=None, out_c8=None, out_c8_ch0=0, epilogue=
 
 
 def launch(d, ref, cfg=0):
-    rc = _ffi.lib().dkt_conv2d_c8(ctypes.byref(d), cfg, _ffi.device_of(ref), _ffi.stream_of(ref))
-    _ffi.check(rc, "dkt_conv2d_c8")
+    _ffi.call("dkt_conv2d_c8", ref, ctypes.byref(d), cfg)
 
 
 def launch_pair(d0, d1, ref, cfg):
     d0.passes = d1.passes = max(d0.passes, d1.passes)          # (one instantiation runs both problems)
-    rc = _ffi.lib().dkt_conv2d_c8_pair(ctypes.byref(d0), ctypes.byref(d1), cfg, _ffi.device_of(ref), _ffi.stream_of(ref))
-    _ffi.check(rc, "dkt_conv2d_c8_pair")
+    _ffi.call("dkt_conv2d_c8_pair", ref, ctypes.byref(d0), ctypes.byref(d1), cfg)
 
 
 def conv2d_c8(srcs, layer, relu=False, out=None, out_c8=None, out_c8_ch0=0, tail=None, cfg=0):
@@ -447,9 +434,7 @@ def pool2x_c8(x, dst, ch0=0):
     """dst[ch0 : ch0 + C] = C8S(avg_pool2d(x, 3, stride=2, padding=1)) (core/update.py:87-88), x fp32 NCHW dense per batch."""
     B, C, H, W = x.shape
     _check_dst("pool2x_c8", dst, B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1, ch0)
-    rc = _ffi.lib().dkt_pool2x_c8(x.data_ptr(), x.stride(0), dst.data_ptr(), dst.bstride_bytes, B, C, H, W, ch0, dst.scale,
-                                  _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_pool2x_c8")
+    _ffi.call("dkt_pool2x_c8", x, x.data_ptr(), x.stride(0), dst.data_ptr(), dst.bstride_bytes, B, C, H, W, ch0, dst.scale)
     return dst
 
 
@@ -457,9 +442,8 @@ def interp_c8(x, dst, ch0=0):
     """dst[ch0 : ch0 + C] = C8S(F.interpolate(x, (dst.H, dst.W), mode="bilinear", align_corners=True)) (core/update.py:93-95)."""
     B, C, H, W = x.shape
     _check_dst("interp_c8", dst, B, C, dst.H, dst.W, ch0)
-    rc = _ffi.lib().dkt_interp_c8(x.data_ptr(), x.stride(0), dst.data_ptr(), dst.bstride_bytes, B, C, H, W, dst.H, dst.W, ch0,
-                                  dst.scale, _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_interp_c8")
+    _ffi.call("dkt_interp_c8", x, x.data_ptr(), x.stride(0), dst.data_ptr(), dst.bstride_bytes, B, C, H, W, dst.H, dst.W, ch0,
+              dst.scale)
     return dst
 
 
@@ -479,8 +463,7 @@ def resample_pair_c8(job0, job1):
         _check_dst("resample_pair_c8", dst, x.shape[0], x.shape[1], dst.H, dst.W, rest[0] if rest else 0)
         jobs.append(_resample_job(0 if kind == "pool" else 1, x, dst, rest[0] if rest else 0))
     x0 = job0[1]
-    rc = _ffi.lib().dkt_resample_pair_c8(ctypes.byref(jobs[0]), ctypes.byref(jobs[1]), _ffi.device_of(x0), _ffi.stream_of(x0))
-    _ffi.check(rc, "dkt_resample_pair_c8")
+    _ffi.call("dkt_resample_pair_c8", x0, ctypes.byref(jobs[0]), ctypes.byref(jobs[1]))
 
 
 def stem7_c8(x, layer, dst, relu=True, ch0=0):
@@ -488,17 +471,14 @@ def stem7_c8(x, layer, dst, relu=True, ch0=0):
     from . import conv as _conv
     B, cin, H, W = x.shape
     w = layer.weight
-    L = _ffi.lib()
     pk = _conv.stem7_packed(layer)
     in_scale = 2.0 ** _conv.in_exp_of(layer)
     if int(w.shape[0]) % 64:
         raise ValueError("stem7_c8: the C8S store writes whole 64-channel blocks (layer has %d outputs)" % int(w.shape[0]))
     _check_dst("stem7_c8", dst, B, int(w.shape[0]), H, W, ch0)
-    rc = L.dkt_conv2d_stem7_c8(x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
-                               None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
-                               dst.data_ptr(), dst.bstride_bytes, ch0, dst.scale, B, cin, int(w.shape[0]), H, W, int(bool(relu)),
-                               _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_stem7_c8")
+    _ffi.call("dkt_conv2d_stem7_c8", x, x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
+              None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
+              dst.data_ptr(), dst.bstride_bytes, ch0, dst.scale, B, cin, int(w.shape[0]), H, W, int(bool(relu)))
     return dst
 
 
@@ -535,8 +515,8 @@ def head_planes(srcs, layer1, layer2, cfg=2):
     s0 = srcs[0]
     hw = _head_weights(layer2)
     nout = int(hw.shape[0])
-    n_co = _ffi.lib().dkt_conv2d_c8_head_blocks(int(layer1.weight.shape[0]), cfg)
-    if n_co <= 0:
+    n_co = _ffi.size("dkt_conv2d_c8_head_blocks", int(layer1.weight.shape[0]), cfg)
+    if n_co == 0:
         raise _ffi.DktError("conv_c8.head: tile shape %d cannot run the head epilogue" % cfg)
     planes = torch.empty((s0.B, nout * n_co * 9, s0.H, s0.W), device=s0.device, dtype=torch.float32)
     d = desc(srcs, layer1, relu=True, epilogue=3, head_w=hw, head_out=planes)
@@ -570,7 +550,6 @@ def motion_front(corr, planes, n_co, head_bias, x_old, x_new, x0, flow, convc1, 
         raise ValueError("motion_front: C8S destinations of another shape")
     if x_new.data_ptr() == x_old.data_ptr():
         raise ValueError("motion_front: x_new must not alias x_old")
-    L = _ffi.lib()
     wf = convf1.weight
     pk = _conv.stem7_packed(convf1)
     in_scale = 2.0 ** _conv.in_exp_of(convf1)
@@ -588,8 +567,7 @@ def motion_front(corr, planes, n_co, head_bias, x_old, x_new, x0, flow, convc1, 
         stem_out_scale=pk.inv_scale / in_scale, stem_in_scale=in_scale, stem_cin=int(wf.shape[1]), stem_cout=int(wf.shape[0]),
         flo_c8=flo.data_ptr(), flo_c8_bstride_bytes=flo.bstride_bytes, flo_c8_ch0=0, flo_act_scale=flo.scale,
         B=B, H=H, W1=W, W2=corr._w2, L=corr.num_levels, r=corr.radius)
-    rc = L.dkt_motion_front_c8(ctypes.byref(d), _ffi.device_of(x_old), _ffi.stream_of(x_old))
-    _ffi.check(rc, "dkt_motion_front_c8")
+    _ffi.call("dkt_motion_front_c8", x_old, ctypes.byref(d))
 
 
 def head(srcs, layer1, layer2, target, diff=None, cfg=2):
@@ -597,16 +575,14 @@ def head(srcs, layer1, layer2, target, diff=None, cfg=2):
     `layer2` a 3x3 layer with 1 or 2 outputs: the hidden tensor is never written -- layer1's epilogue reduces it against
     layer2's weights tap by tap (epilogue 3), dkt_head_finish adds the shifted planes.  diff = (ref, dst): dst = target - ref."""
     s0 = srcs[0]
-    L = _ffi.lib()
     planes, n_co = head_planes(srcs, layer1, layer2, cfg)
     nout = planes.shape[1] // (n_co * 9)
     b2 = layer2.bias
     ref, dst = diff if diff is not None else (None, None)
-    rc = L.dkt_head_finish(planes.data_ptr(), planes.stride(0), n_co, None if b2 is None else b2.detach().data_ptr(),
-                           target.data_ptr(), target.stride(0), None if ref is None else ref.data_ptr(),
-                           0 if ref is None else ref.stride(0), None if dst is None else dst.data_ptr(),
-                           0 if dst is None else dst.stride(0), s0.B, nout, s0.H, s0.W, _ffi.device_of(planes), _ffi.stream_of(planes))
-    _ffi.check(rc, "dkt_head_finish")
+    _ffi.call("dkt_head_finish", planes, planes.data_ptr(), planes.stride(0), n_co, None if b2 is None else b2.detach().data_ptr(),
+              target.data_ptr(), target.stride(0), None if ref is None else ref.data_ptr(),
+              0 if ref is None else ref.stride(0), None if dst is None else dst.data_ptr(),
+              0 if dst is None else dst.stride(0), s0.B, nout, s0.H, s0.W)
     return target
 
 
@@ -628,14 +604,12 @@ def stem7_dual(x, layer, out, dst, relu=True):
     from . import conv as _conv
     B, cin, H, W = x.shape
     w = layer.weight
-    L = _ffi.lib()
     pk = _conv.stem7_packed(layer)
     in_scale = 2.0 ** _conv.in_exp_of(layer)
-    rc = L.dkt_conv2d_stem7_dual(x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
-                                 None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
-                                 out.data_ptr(), out.stride(0), dst.data_ptr(), dst.bstride_bytes, 0, dst.scale,
-                                 B, cin, int(w.shape[0]), H, W, int(bool(relu)), _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_conv2d_stem7_dual")
+    _ffi.call("dkt_conv2d_stem7_dual", x, x.data_ptr(), x.stride(0), pk.hi.data_ptr(), pk.lo.data_ptr(),
+              None if pk.bias is None else pk.bias.data_ptr(), pk.inv_scale / in_scale, in_scale,
+              out.data_ptr(), out.stride(0), dst.data_ptr(), dst.bstride_bytes, 0, dst.scale,
+              B, cin, int(w.shape[0]), H, W, int(bool(relu)))
     return out
 
 
@@ -649,10 +623,9 @@ def norm_join_c8(c, c_params, c_relu=True, a=None, a_params=None, a_relu=False, 
         raise ValueError("norm_join_c8: dense fp32 NCHW tensors of one shape")
     if dst is not None and (dst.H, dst.W, dst.B) != (H, W, B):
         raise ValueError("norm_join_c8: C8S destination of another size")
-    rc = _ffi.lib().dkt_instance_norm_join_c8(
-        c.data_ptr(), c_params.data_ptr(), int(bool(c_relu)), None if a is None else a.data_ptr(),
+    _ffi.call(
+        "dkt_instance_norm_join_c8", c, c.data_ptr(), c_params.data_ptr(), int(bool(c_relu)), None if a is None else a.data_ptr(),
         None if a_params is None else a_params.data_ptr(), int(bool(a_relu)), None if y is None else y.data_ptr(),
         None if dst is None else dst.data_ptr(), 0 if dst is None else dst.bstride_bytes, ch0,
-        1.0 if dst is None else dst.scale, B, C, H, W, _ffi.device_of(c), _ffi.stream_of(c))
-    _ffi.check(rc, "dkt_instance_norm_join_c8")
+        1.0 if dst is None else dst.scale, B, C, H, W)
     return y if y is not None else dst

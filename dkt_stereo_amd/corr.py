@@ -41,10 +41,8 @@ def _build_pyramid(fmap1, fmap2, num_levels, divisor, out=None):
     else:
         pyr = [torch.empty((N, 1, 1, W2 >> i), device=fmap1.device, dtype=torch.float32)
                for i in range(num_levels)]
-    rc = _ffi.lib().dkt_corr1d_build(fmap1.data_ptr(), fmap2.data_ptr(), _ffi.ptr_array(pyr),
-                                     B, C, H, W1, W2, num_levels, float(divisor),
-                                     _ffi.device_of(fmap1), _ffi.stream_of(fmap1))
-    _ffi.check(rc, "dkt_corr1d_build")
+    _ffi.call("dkt_corr1d_build", fmap1, fmap1.data_ptr(), fmap2.data_ptr(), _ffi.ptr_array(pyr),
+              B, C, H, W1, W2, num_levels, float(divisor))
     return pyr
 
 
@@ -57,22 +55,18 @@ def _lookup(pyramid, coords, radius, w2, skewed=False):
     K = 2 * radius + 1
     out = torch.empty((B, L * K, H, W1), device=coords.device, dtype=torch.float32)
     # only channel 0 (x) is read, like coords[:, :1] in core/corr.py:129
-    fn = _ffi.lib().dkt_corr1d_lookup_skew if skewed else _ffi.lib().dkt_corr1d_lookup
-    rc = fn(_ffi.ptr_array(pyramid), coords.data_ptr(), coords.stride(0), out.data_ptr(), B, H, W1, w2, L,
-            radius, _ffi.device_of(coords), _ffi.stream_of(coords))
-    _ffi.check(rc, "dkt_corr1d_lookup_skew" if skewed else "dkt_corr1d_lookup")
+    _ffi.call("dkt_corr1d_lookup_skew" if skewed else "dkt_corr1d_lookup", coords,
+              _ffi.ptr_array(pyramid), coords.data_ptr(), coords.stride(0), out.data_ptr(), B, H, W1, w2, L, radius)
     return out
 
 
 def _skew_pyramid(pyramid, B, H, W1, W2, out=None):
     """dkt_corr1d_skew: diagonal-major copy of every level (see corr1d_skew.hip)."""
     if out is None:
-        pitch = _ffi.lib().dkt_corr1d_skew_pitch(W1)
+        pitch = _ffi.size("dkt_corr1d_skew_pitch", W1)
         out = [torch.empty((B * H, W2 >> i, pitch), device=p.device, dtype=torch.float32)
                for i, p in enumerate(pyramid)]
-    rc = _ffi.lib().dkt_corr1d_skew(_ffi.ptr_array(pyramid), _ffi.ptr_array(out), B, H, W1, W2, len(pyramid),
-                                    _ffi.device_of(pyramid[0]), _ffi.stream_of(pyramid[0]))
-    _ffi.check(rc, "dkt_corr1d_skew")
+    _ffi.call("dkt_corr1d_skew", pyramid[0], _ffi.ptr_array(pyramid), _ffi.ptr_array(out), B, H, W1, W2, len(pyramid))
     return out
 
 
@@ -97,9 +91,7 @@ class _BuildFn(torch.autograd.Function):
         glv = [g.contiguous() if g is not None else torch.zeros((N, 1, 1, W2 >> i), device=f1.device)
                for i, g in enumerate(glv)]
         gvol = torch.empty((N, W2), device=f1.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_corr1d_pool_bwd(_ffi.ptr_array(glv), gvol.data_ptr(), B, H, W1, W2, L, float(divisor),
-                                            _ffi.device_of(gvol), _ffi.stream_of(gvol))
-        _ffi.check(rc, "dkt_corr1d_pool_bwd")
+        _ffi.call("dkt_corr1d_pool_bwd", gvol, _ffi.ptr_array(glv), gvol.data_ptr(), B, H, W1, W2, L, float(divisor))
         G = gvol.view(B, H, W1, W2)
         gf1 = torch.einsum('bhwv,bchv->bchw', G, f2.float()) if ctx.needs_input_grad[0] else None
         gf2 = torch.einsum('bhwv,bchw->bchv', G, f1.float()) if ctx.needs_input_grad[1] else None
@@ -126,10 +118,8 @@ class _LookupFn(torch.autograd.Function):
             coords = coords.contiguous()
         gout = gout.contiguous().float()
         grads = [torch.zeros(s, device=gout.device, dtype=torch.float32) for s in shapes]
-        rc = _ffi.lib().dkt_corr1d_lookup_bwd(gout.data_ptr(), coords.data_ptr(), coords.stride(0),
-                                              _ffi.ptr_array(grads), B, H, W1, w2, len(grads), radius,
-                                              _ffi.device_of(gout), _ffi.stream_of(gout))
-        _ffi.check(rc, "dkt_corr1d_lookup_bwd")
+        _ffi.call("dkt_corr1d_lookup_bwd", gout, gout.data_ptr(), coords.data_ptr(), coords.stride(0),
+                  _ffi.ptr_array(grads), B, H, W1, w2, len(grads), radius)
         return (None, None, None, None) + tuple(grads)
 
 
@@ -227,22 +217,20 @@ class CorrBlock1D:
             # straight into the C8S operand of the next convolution (conv_c8.hip); four levels only
             if self.num_levels != 4 or tap:
                 return None
-            rc = _ffi.lib().dkt_corr1d_lookup_conv1x1_c8(
+            _ffi.call(
+                "dkt_corr1d_lookup_conv1x1_c8", coords,
                 _ffi.ptr_array(self._skew), coords.data_ptr(), coords.stride(0), wm.data_ptr(),
                 None if bias is None else bias.detach().data_ptr(), out_c8.data_ptr(), out_c8.bstride_bytes, out_c8_ch0,
-                out_c8.scale, B, H, W1, self._w2, self.num_levels, self.radius, cout, int(bool(relu)),
-                _ffi.device_of(coords), _ffi.stream_of(coords))
-            _ffi.check(rc, "dkt_corr1d_lookup_conv1x1_c8")
+                out_c8.scale, B, H, W1, self._w2, self.num_levels, self.radius, cout, int(bool(relu)))
             return out_c8
         out = torch.empty((B, cout, H, W1), device=coords.device, dtype=torch.float32)
         tp = torch.empty((B, self.num_levels * K, H, W1), device=coords.device, dtype=torch.float32) if tap else None
-        rc = _ffi.lib().dkt_corr1d_lookup_conv1x1(
+        _ffi.call(
+            "dkt_corr1d_lookup_conv1x1", coords,
             _ffi.ptr_array(self._skew), coords.data_ptr(), coords.stride(0), wm.data_ptr(),
             None if bias is None else bias.detach().data_ptr(), out.data_ptr(), out.stride(0),
             None if tp is None else tp.data_ptr(), 0 if tp is None else tp.stride(0),
-            B, H, W1, self._w2, self.num_levels, self.radius, cout, int(bool(relu)),
-            _ffi.device_of(coords), _ffi.stream_of(coords))
-        _ffi.check(rc, "dkt_corr1d_lookup_conv1x1")
+            B, H, W1, self._w2, self.num_levels, self.radius, cout, int(bool(relu)))
         return (out, tp) if tap else out
 
     @staticmethod
@@ -322,9 +310,7 @@ class CorrBlock1D_Cosine(CorrBlock1D):
         _ffi.require_gpu(fmap)
         B, C, H, W = fmap.shape
         out = torch.empty_like(fmap)
-        rc = _ffi.lib().dkt_l2norm_channels(fmap.data_ptr(), out.data_ptr(), B, C, H * W,
-                                            _ffi.device_of(fmap), _ffi.stream_of(fmap))
-        _ffi.check(rc, "dkt_l2norm_channels")
+        _ffi.call("dkt_l2norm_channels", fmap, fmap.data_ptr(), out.data_ptr(), B, C, H * W)
         return out
 
     @staticmethod
@@ -354,9 +340,7 @@ class PytorchAlternateCorrBlock1D:
         for i in range(1, num_levels):
             src = self._f2pyr[-1]
             dst = torch.empty((B, C, H, src.shape[3] // 2), device=src.device, dtype=torch.float32)
-            rc = _ffi.lib().dkt_pool_w(src.data_ptr(), dst.data_ptr(), B * C * H, src.shape[3],
-                                       _ffi.device_of(src), _ffi.stream_of(src))
-            _ffi.check(rc, "dkt_pool_w")
+            _ffi.call("dkt_pool_w", src, src.data_ptr(), dst.data_ptr(), B * C * H, src.shape[3])
             self._f2pyr.append(dst)
 
     def __call__(self, coords):
@@ -366,11 +350,8 @@ class PytorchAlternateCorrBlock1D:
         W2 = self.fmap2.shape[3]
         K = 2 * self.radius + 1
         out = torch.empty((B, self.num_levels * K, H, W1), device=coords.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_corr1d_lookup_otf(self.fmap1.data_ptr(), _ffi.ptr_array(self._f2pyr),
-                                              coords.data_ptr(), out.data_ptr(), B, C, H, W1, W2,
-                                              self.num_levels, self.radius,
-                                              _ffi.device_of(coords), _ffi.stream_of(coords))
-        _ffi.check(rc, "dkt_corr1d_lookup_otf")
+        _ffi.call("dkt_corr1d_lookup_otf", coords, self.fmap1.data_ptr(), _ffi.ptr_array(self._f2pyr),
+                  coords.data_ptr(), out.data_ptr(), B, C, H, W1, W2, self.num_levels, self.radius)
         return out
 
 

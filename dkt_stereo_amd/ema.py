@@ -119,9 +119,8 @@ def ema_kernel(ts, ss, decay, absmax=None):
         return
     dev = ts[0].device
     _, ptr, _ = flat_tables(dev, ts, ss)
-    rc = _ffi.lib().dkt_ema_update(ptr[0], ptr[1], ptr[2], len(ts), float(decay), float(1 - decay),
-                                   None if absmax is None else absmax.data_ptr(), _ffi.device_of(ts[0]), _ffi.stream_of(ts[0]))
-    _ffi.check(rc, "dkt_ema_update")
+    _ffi.call("dkt_ema_update", ts[0], ptr[0], ptr[1], ptr[2], len(ts), float(decay), float(1 - decay),
+              None if absmax is None else absmax.data_ptr())
 
 
 def _kernel_ok(t, s):

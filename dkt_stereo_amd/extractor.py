@@ -72,12 +72,9 @@ def norm_act(norm, x, relu):
     if (isinstance(norm, nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats and _hip_ok(x)):
         x = x.contiguous()
         n, c, h, w = x.shape
-        L = _ffi.lib()
-        ws = torch.empty(L.dkt_instance_norm_workspace(n * c, h * w), device=x.device, dtype=torch.uint8)
+        ws = torch.empty(_ffi.size("dkt_instance_norm_workspace", n * c, h * w), device=x.device, dtype=torch.uint8)
         y = torch.empty_like(x)
-        rc = L.dkt_instance_norm(x.data_ptr(), y.data_ptr(), ws.data_ptr(), n * c, h * w, float(norm.eps),
-                                 int(relu), _ffi.device_of(x), _ffi.stream_of(x))
-        _ffi.check(rc, "dkt_instance_norm")
+        _ffi.call("dkt_instance_norm", x, x.data_ptr(), y.data_ptr(), ws.data_ptr(), n * c, h * w, float(norm.eps), int(relu))
         return y
     y = norm(x)
     return F.relu(y) if relu else y
@@ -156,17 +153,13 @@ def instance_norm_params(norm, x, stats=None):
     convolution that produced x left behind -- the statistics pass is skipped."""
     x = x if x.is_contiguous() else x.contiguous()
     n, c, h, w = x.shape
-    L = _ffi.lib()
     out = torch.empty((n * c, 2), device=x.device, dtype=torch.float32)
     if stats is not None:
         ws = stats.part
     else:
-        ws = torch.empty(L.dkt_instance_norm_workspace(n * c, h * w), device=x.device, dtype=torch.uint8)
-        rc = L.dkt_instance_norm_stats(x.data_ptr(), ws.data_ptr(), n * c, h * w, _ffi.device_of(x), _ffi.stream_of(x))
-        _ffi.check(rc, "dkt_instance_norm_stats")
-    rc = L.dkt_instance_norm_finalize(ws.data_ptr(), n * c, h * w, float(norm.eps), out.data_ptr(),
-                                      _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_instance_norm_finalize")
+        ws = torch.empty(_ffi.size("dkt_instance_norm_workspace", n * c, h * w), device=x.device, dtype=torch.uint8)
+        _ffi.call("dkt_instance_norm_stats", x, x.data_ptr(), ws.data_ptr(), n * c, h * w)
+    _ffi.call("dkt_instance_norm_finalize", x, ws.data_ptr(), n * c, h * w, float(norm.eps), out.data_ptr())
     return out
 
 
@@ -189,22 +182,18 @@ def norm_add_relu(norm, x, c, c_stats=None):
         x = x.contiguous()
         c = c.contiguous()
         n, ch, h, w = c.shape
-        L = _ffi.lib()
         y = torch.empty_like(c)
         if c_stats is not None:
             ws = c_stats.part
         else:
-            ws = torch.empty(L.dkt_instance_norm_workspace(n * ch, h * w), device=c.device, dtype=torch.uint8)
-            rc = L.dkt_instance_norm_stats(c.data_ptr(), ws.data_ptr(), n * ch, h * w, _ffi.device_of(c), _ffi.stream_of(c))
-            _ffi.check(rc, "dkt_instance_norm_stats")
-        if lazy is not None:
-            rc = L.dkt_instance_norm_add_relu_lazy(x.data_ptr(), lazy.params.data_ptr(), int(lazy.relu), c.data_ptr(),
-                                                   y.data_ptr(), ws.data_ptr(), n * ch, h * w, float(norm.eps),
-                                                   _ffi.device_of(c), _ffi.stream_of(c))
+            ws = torch.empty(_ffi.size("dkt_instance_norm_workspace", n * ch, h * w), device=c.device, dtype=torch.uint8)
+            _ffi.call("dkt_instance_norm_stats", c, c.data_ptr(), ws.data_ptr(), n * ch, h * w)
+        if lazy is not None:                 # (logged under the eager join's name, as the launch counts have always seen it)
+            _ffi.call("dkt_instance_norm_add_relu_lazy", c, x.data_ptr(), lazy.params.data_ptr(), int(lazy.relu), c.data_ptr(),
+                      y.data_ptr(), ws.data_ptr(), n * ch, h * w, float(norm.eps), log="dkt_instance_norm_add_relu")
         else:
-            rc = L.dkt_instance_norm_add_relu(x.data_ptr(), c.data_ptr(), y.data_ptr(), ws.data_ptr(), n * ch, h * w,
-                                              float(norm.eps), _ffi.device_of(c), _ffi.stream_of(c))
-        _ffi.check(rc, "dkt_instance_norm_add_relu")
+            _ffi.call("dkt_instance_norm_add_relu", c, x.data_ptr(), c.data_ptr(), y.data_ptr(), ws.data_ptr(), n * ch, h * w,
+                      float(norm.eps))
         return y
     if lazy is not None:
         x = lazy.materialize()
@@ -235,9 +224,7 @@ def add_relu(a, b):
     """relu(a + b), one pass (dkt_add_relu)."""
     if _hip_ok(a) and _hip_ok(b) and a.shape == b.shape and a.is_contiguous() and b.is_contiguous():
         y = torch.empty_like(a)
-        rc = _ffi.lib().dkt_add_relu(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(),
-                                     _ffi.device_of(a), _ffi.stream_of(a))
-        _ffi.check(rc, "dkt_add_relu")
+        _ffi.call("dkt_add_relu", a, a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel())
         return y
     return F.relu(a + b)
 

@@ -71,8 +71,7 @@ def _launch(jobs, B, H, W, device, inputs):
     arr = (_ffi.FandeJob * len(jobs))(*jobs)
     ws = torch.empty(_ffi.FANDE_WS_DOUBLES_PER_IMAGE * B * len(jobs), device=device, dtype=torch.float64)
     with torch.cuda.device(device):
-        _ffi.check(_ffi.lib().dkt_fande(arr, len(jobs), B, H, W, ws.data_ptr(), _ffi.device_of(ws),
-                                        _ffi.stream_of(ws)), "dkt_fande")
+        _ffi.call("dkt_fande", ws, arr, len(jobs), B, H, W, ws.data_ptr())
 
 
 def FandE_Filter(source, target, valid, withprob=False, threshold=3):

@@ -29,8 +29,7 @@ def _pool_geo(geo_volume, num_levels, out=None):
         src = pyr[-1]
         di = src.shape[2]
         dst = out[i] if out is not None else torch.empty((b, c, di // 2, h, w), device=src.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_pool_d(src.data_ptr(), dst.data_ptr(), b * c, di, h * w, _ffi.device_of(src), _ffi.stream_of(src))
-        _ffi.check(rc, "dkt_pool_d")
+        _ffi.call("dkt_pool_d", src, src.data_ptr(), dst.data_ptr(), b * c, di, h * w)
         pyr.append(dst)
     return pyr
 
@@ -50,9 +49,7 @@ class _GeoPyramidFn(torch.autograd.Function):
         glv = [g.contiguous() if g is not None else torch.zeros((b, c, d >> i, h, w), device=dev)
                for i, g in enumerate(glv)]
         out = torch.empty((b, c, d, h, w), device=dev, dtype=torch.float32)
-        rc = _ffi.lib().dkt_geo_pool_bwd(_ffi.ptr_array(glv), out.data_ptr(), b * c, d, h * w, L,
-                                         _ffi.device_of(out), _ffi.stream_of(out))
-        _ffi.check(rc, "dkt_geo_pool_bwd")
+        _ffi.call("dkt_geo_pool_bwd", out, _ffi.ptr_array(glv), out.data_ptr(), b * c, d, h * w, L)
         return out, None
 
 
@@ -76,11 +73,9 @@ class _GeoLookupFn(torch.autograd.Function):
         b, c, d, h, w = vol._shape
         gout = gout.contiguous().float()
         grads = [torch.zeros(s, device=gout.device, dtype=torch.float32) for s in ctx.shapes]
-        rc = _ffi.lib().dkt_geo_lookup_bwd(gout.data_ptr(), disp.data_ptr(), coords.data_ptr(),
-                                           _ffi.ptr_array(grads[:L]), _ffi.ptr_array(grads[L:]),
-                                           b, c, d, h, w, vol._w2, L, vol.radius,
-                                           _ffi.device_of(gout), _ffi.stream_of(gout))
-        _ffi.check(rc, "dkt_geo_lookup_bwd")
+        _ffi.call("dkt_geo_lookup_bwd", gout, gout.data_ptr(), disp.data_ptr(), coords.data_ptr(),
+                  _ffi.ptr_array(grads[:L]), _ffi.ptr_array(grads[L:]),
+                  b, c, d, h, w, vol._w2, L, vol.radius)
         return (None, None, None) + tuple(grads)
 
 
@@ -150,11 +145,9 @@ class Combined_Geo_Encoding_Volume:
         b, c, d, h, w = self._shape
         K = 2 * self.radius + 1
         out = torch.empty((b, self.num_levels * K * (c + 1), h, w), device=disp.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_geo_lookup(_ffi.ptr_array(geo_pyr), _ffi.ptr_array(init_pyr),
-                                       disp.data_ptr(), coords.data_ptr(), out.data_ptr(),
-                                       b, c, d, h, w, self._w2, self.num_levels, self.radius,
-                                       _ffi.device_of(disp), _ffi.stream_of(disp))
-        _ffi.check(rc, "dkt_geo_lookup")
+        _ffi.call("dkt_geo_lookup", disp, _ffi.ptr_array(geo_pyr), _ffi.ptr_array(init_pyr),
+                  disp.data_ptr(), coords.data_ptr(), out.data_ptr(),
+                  b, c, d, h, w, self._w2, self.num_levels, self.radius)
         return out
 
     def __call__(self, disp, coords):
@@ -194,16 +187,14 @@ class Combined_Geo_Encoding_Volume:
         bias = layer.bias
         out = None if out_c8 is not None else torch.empty((b, cout, h, wd), device=disp.device, dtype=torch.float32)
         tp = torch.empty((b, w.shape[1], h, wd), device=disp.device, dtype=torch.float32) if tap else None
-        rc = _ffi.lib().dkt_geo_lookup_conv1x1(
-            _ffi.ptr_array(self.geo_volume_pyramid), _ffi.ptr_array(self.init_corr_pyramid),
+        _ffi.call(
+            "dkt_geo_lookup_conv1x1", disp, _ffi.ptr_array(self.geo_volume_pyramid), _ffi.ptr_array(self.init_corr_pyramid),
             disp.data_ptr(), disp.stride(0), coords.data_ptr(), wm.data_ptr(),
             None if bias is None else bias.detach().data_ptr(),
             None if out is None else out.data_ptr(), 0 if out is None else out.stride(0),
             None if out_c8 is None else out_c8.data_ptr(), 0 if out_c8 is None else out_c8.bstride_bytes, out_c8_ch0,
             1.0 if out_c8 is None else out_c8.scale, None if tp is None else tp.data_ptr(), 0 if tp is None else tp.stride(0),
-            b, c, d, h, wd, self._w2, self.num_levels, self.radius, cout, int(bool(relu)),
-            _ffi.device_of(disp), _ffi.stream_of(disp))
-        _ffi.check(rc, "dkt_geo_lookup_conv1x1")
+            b, c, d, h, wd, self._w2, self.num_levels, self.radius, cout, int(bool(relu)))
         res = out if out_c8 is None else out_c8
         return (res, tp) if tap else res
 

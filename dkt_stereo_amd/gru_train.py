@@ -42,10 +42,8 @@ class _GateZrFn(torch.autograd.Function):
         azr = azr.contiguous()
         (cz, cz_bs), (cr, cr_bs), (h, h_bs) = _strided(cz), _strided(cr), _strided(h)
         z, r, rh = (torch.empty((B, Ch, H, W), device=h.device, dtype=torch.float32) for _ in range(3))
-        rc = _ffi.lib().dkt_gru_gate_zr_train(azr.data_ptr(), cz.data_ptr(), cz_bs, cr.data_ptr(), cr_bs, h.data_ptr(), h_bs,
-                                              z.data_ptr(), r.data_ptr(), rh.data_ptr(), Ch * H * W, B, Ch, H * W,
-                                              _ffi.device_of(h), _ffi.stream_of(h))
-        _ffi.check(rc, "dkt_gru_gate_zr_train")
+        _ffi.call("dkt_gru_gate_zr_train", h, azr.data_ptr(), cz.data_ptr(), cz_bs, cr.data_ptr(), cr_bs, h.data_ptr(), h_bs,
+                  z.data_ptr(), r.data_ptr(), rh.data_ptr(), Ch * H * W, B, Ch, H * W)
         ctx.save_for_backward(z, r, h)
         ctx.h_bs = h_bs
         return z, rh
@@ -63,10 +61,8 @@ class _GateZrFn(torch.autograd.Function):
         grh, grh_bs = _strided(grh)
         gazr = torch.empty((B, 2 * Ch, H, W), device=z.device, dtype=torch.float32) if need_a else None
         gh = torch.empty_like(z) if need_h else None
-        rc = _ffi.lib().dkt_gru_gate_zr_bwd(gz.data_ptr(), grh.data_ptr(), grh_bs, z.data_ptr(), r.data_ptr(), h.data_ptr(),
-                                            ctx.h_bs, _ffi.ptr(gazr), _ffi.ptr(gh), B, Ch, H * W,
-                                            _ffi.device_of(z), _ffi.stream_of(z))
-        _ffi.check(rc, "dkt_gru_gate_zr_bwd")
+        _ffi.call("dkt_gru_gate_zr_bwd", z, gz.data_ptr(), grh.data_ptr(), grh_bs, z.data_ptr(), r.data_ptr(), h.data_ptr(),
+                  ctx.h_bs, _ffi.ptr(gazr), _ffi.ptr(gh), B, Ch, H * W)
         na, ncz, ncr = ctx.needs_input_grad[:3]
         # the gradients of cz and cr are the halves of gazr: views, no further writes
         return (gazr if na else None, gazr[:, :Ch] if ncz else None, gazr[:, Ch:] if ncr else None, gh)
@@ -83,10 +79,8 @@ class _GateOutFn(torch.autograd.Function):
         aq, z = aq.contiguous(), z.contiguous()
         (cq, cq_bs), (h, h_bs) = _strided(cq), _strided(h)
         q, out = (torch.empty((B, Ch, H, W), device=h.device, dtype=torch.float32) for _ in range(2))
-        rc = _ffi.lib().dkt_gru_gate_out_train(aq.data_ptr(), cq.data_ptr(), cq_bs, z.data_ptr(), h.data_ptr(), h_bs,
-                                               q.data_ptr(), out.data_ptr(), Ch * H * W, B, Ch, H * W,
-                                               _ffi.device_of(h), _ffi.stream_of(h))
-        _ffi.check(rc, "dkt_gru_gate_out_train")
+        _ffi.call("dkt_gru_gate_out_train", h, aq.data_ptr(), cq.data_ptr(), cq_bs, z.data_ptr(), h.data_ptr(), h_bs,
+                  q.data_ptr(), out.data_ptr(), Ch * H * W, B, Ch, H * W)
         ctx.save_for_backward(z, q, h)
         ctx.h_bs = h_bs
         return out
@@ -103,10 +97,8 @@ class _GateOutFn(torch.autograd.Function):
         gaq = torch.empty_like(z) if (naq or ncq) else None
         gz = torch.empty_like(z) if nz else None
         gh = torch.empty_like(z) if nh else None
-        rc = _ffi.lib().dkt_gru_gate_out_bwd(gout.data_ptr(), g_bs, z.data_ptr(), q.data_ptr(), h.data_ptr(), ctx.h_bs,
-                                             _ffi.ptr(gaq), _ffi.ptr(gz), _ffi.ptr(gh), B, Ch, H * W,
-                                             _ffi.device_of(z), _ffi.stream_of(z))
-        _ffi.check(rc, "dkt_gru_gate_out_bwd")
+        _ffi.call("dkt_gru_gate_out_bwd", z, gout.data_ptr(), g_bs, z.data_ptr(), q.data_ptr(), h.data_ptr(), ctx.h_bs,
+                  _ffi.ptr(gaq), _ffi.ptr(gz), _ffi.ptr(gh), B, Ch, H * W)
         return gaq if naq else None, gaq if ncq else None, gz, gh
 
 
@@ -117,8 +109,7 @@ class _Pool2xFn(torch.autograd.Function):
         x = x.contiguous()
         B, C, H, W = x.shape
         y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), device=x.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_pool2x(x.data_ptr(), y.data_ptr(), B * C, H, W, _ffi.device_of(x), _ffi.stream_of(x))
-        _ffi.check(rc, "dkt_pool2x")
+        _ffi.call("dkt_pool2x", x, x.data_ptr(), y.data_ptr(), B * C, H, W)
         ctx.shape = (B, C, H, W)
         return y
 
@@ -130,8 +121,7 @@ class _Pool2xFn(torch.autograd.Function):
         B, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty(ctx.shape, device=gy.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_pool2x_bwd(gy.data_ptr(), gx.data_ptr(), B * C, H, W, _ffi.device_of(gy), _ffi.stream_of(gy))
-        _ffi.check(rc, "dkt_pool2x_bwd")
+        _ffi.call("dkt_pool2x_bwd", gy, gy.data_ptr(), gx.data_ptr(), B * C, H, W)
         return gx
 
 
@@ -142,9 +132,7 @@ class _InterpFn(torch.autograd.Function):
         x = x.contiguous()
         B, C, H, W = x.shape
         y = torch.empty((B, C, Ho, Wo), device=x.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_interp_bilinear(x.data_ptr(), y.data_ptr(), B * C, H, W, Ho, Wo,
-                                            _ffi.device_of(x), _ffi.stream_of(x))
-        _ffi.check(rc, "dkt_interp_bilinear")
+        _ffi.call("dkt_interp_bilinear", x, x.data_ptr(), y.data_ptr(), B * C, H, W, Ho, Wo)
         ctx.shape = (B, C, H, W)
         return y
 
@@ -156,9 +144,7 @@ class _InterpFn(torch.autograd.Function):
         B, C, H, W = ctx.shape
         gy = gy.contiguous()
         gx = torch.empty(ctx.shape, device=gy.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_interp_bilinear_bwd(gy.data_ptr(), gx.data_ptr(), B * C, H, W, gy.shape[2], gy.shape[3],
-                                                _ffi.device_of(gy), _ffi.stream_of(gy))
-        _ffi.check(rc, "dkt_interp_bilinear_bwd")
+        _ffi.call("dkt_interp_bilinear_bwd", gy, gy.data_ptr(), gx.data_ptr(), B * C, H, W, gy.shape[2], gy.shape[3])
         return gx, None, None
 
 

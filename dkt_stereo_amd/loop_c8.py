@@ -389,9 +389,7 @@ class C8Loop:
             if t.dtype != torch.float32:
                 t = t.float()
             src, count = t.data_ptr(), t.numel()
-        rc = _ffi.lib().dkt_loop_status(jobs, n, src, count, self.err.data_ptr(), buf.data_ptr(), _ffi.device_of(self.err),
-                                        _ffi.stream_of(self.err))
-        _ffi.check(rc, "dkt_loop_status")
+        _ffi.call("dkt_loop_status", self.err, jobs, n, src, count, self.err.data_ptr(), buf.data_ptr())
         words = buf.cpu().numpy()                          # the forward's one host synchronisation
         maxima = words[2:].astype(np.uint16).view(np.float16).astype(np.float32)
         ok = True

@@ -57,10 +57,9 @@ class _SeqLoss(torch.autograd.Function):
             d.mask[k], d.loss[k] = masks[k].data_ptr(), losses[k].data_ptr()
         d.max_flow = max_flow
         d.rec, d.B, d.H, d.W = rec.data_ptr(), B, H, W
-        L = _ffi.lib()
-        ws = torch.empty(L.dkt_seq_loss_ws_doubles(K, n, B, H, W), device=dev, dtype=torch.float64)
+        ws = torch.empty(_ffi.size("dkt_seq_loss_ws_doubles", K, n, B, H, W), device=dev, dtype=torch.float64)
         with torch.cuda.device(dev):
-            _ffi.check(L.dkt_seq_loss(d, ws.data_ptr(), _ffi.device_of(ws), _ffi.stream_of(ws)), "dkt_seq_loss")
+            _ffi.call("dkt_seq_loss", ws, d, ws.data_ptr())
         ctx.desc, ctx.K, ctx.n = d, K, n
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(*masks, rec)
@@ -85,8 +84,7 @@ class _SeqLoss(torch.autograd.Function):
             out.append(t)
             g.grad[i] = t.data_ptr()
         with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().dkt_seq_loss_bwd(ctx.desc, g, _ffi.device_of(preds[0]), _ffi.stream_of(preds[0])),
-                       "dkt_seq_loss_bwd")
+            _ffi.call("dkt_seq_loss_bwd", preds[0], ctx.desc, g)
         return (None,) + (None,) * (2 * ctx.K) + tuple(out)
 
 

@@ -27,14 +27,13 @@ def _require_planes(x):
         raise _ffi.DktError("the instance-norm training nodes take non-empty (N, C, H, W) tensors (got %s)" % (tuple(x.shape),))
 
 
-def _bytes(n, device):
-    return torch.empty(n, device=device, dtype=torch.uint8)
+def _workspace(query, planes, HW, device):
+    return torch.empty(_ffi.size(query, planes, HW), device=device, dtype=torch.uint8)
 
 
-def _finalize(L, ws, planes, HW, eps, x):
+def _finalize(ws, planes, HW, eps, x):
     mi = torch.empty((planes, 2), device=x.device, dtype=torch.float32)
-    rc = L.dkt_instance_norm_finalize(ws.data_ptr(), planes, HW, eps, mi.data_ptr(), _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_instance_norm_finalize")
+    _ffi.call("dkt_instance_norm_finalize", x, ws.data_ptr(), planes, HW, eps, mi.data_ptr())
     return mi
 
 
@@ -46,13 +45,10 @@ class _InstanceNormFn(torch.autograd.Function):
         x = x.contiguous()
         n, c, h, w = x.shape
         planes, HW = n * c, h * w
-        L = _ffi.lib()
-        ws = _bytes(L.dkt_instance_norm_workspace(planes, HW), x.device)
+        ws = _workspace("dkt_instance_norm_workspace", planes, HW, x.device)
         y = torch.empty_like(x)
-        rc = L.dkt_instance_norm(x.data_ptr(), y.data_ptr(), ws.data_ptr(), planes, HW, eps, int(relu),
-                                 _ffi.device_of(x), _ffi.stream_of(x))
-        _ffi.check(rc, "dkt_instance_norm")
-        ctx.save_for_backward(x, _finalize(L, ws, planes, HW, eps, x))
+        _ffi.call("dkt_instance_norm", x, x.data_ptr(), y.data_ptr(), ws.data_ptr(), planes, HW, eps, int(relu))
+        ctx.save_for_backward(x, _finalize(ws, planes, HW, eps, x))
         ctx.relu = bool(relu)
         return y
 
@@ -66,12 +62,10 @@ class _InstanceNormFn(torch.autograd.Function):
         gy = gy.contiguous()
         n, c, h, w = x.shape
         planes, HW = n * c, h * w
-        L = _ffi.lib()
-        ws = _bytes(L.dkt_instance_norm_bwd_workspace(planes, HW), x.device)
+        ws = _workspace("dkt_instance_norm_bwd_workspace", planes, HW, x.device)
         gx = torch.empty_like(x)
-        rc = L.dkt_instance_norm_bwd(gy.data_ptr(), x.data_ptr(), mi.data_ptr(), int(ctx.relu), gx.data_ptr(), ws.data_ptr(),
-                                     planes, HW, _ffi.device_of(x), _ffi.stream_of(x))
-        _ffi.check(rc, "dkt_instance_norm_bwd")
+        _ffi.call("dkt_instance_norm_bwd", x, gy.data_ptr(), x.data_ptr(), mi.data_ptr(), int(ctx.relu), gx.data_ptr(),
+                  ws.data_ptr(), planes, HW)
         return gx, None, None
 
 
@@ -85,15 +79,12 @@ class _InstanceNormAddReluFn(torch.autograd.Function):
         a, c = a.contiguous(), c.contiguous()
         n, ch, h, w = c.shape
         planes, HW = n * ch, h * w
-        L = _ffi.lib()
-        dev, st = _ffi.device_of(c), _ffi.stream_of(c)
-        ws = _bytes(L.dkt_instance_norm_workspace(planes, HW), c.device)
+        ws = _workspace("dkt_instance_norm_workspace", planes, HW, c.device)
         out = torch.empty_like(c)
-        _ffi.check(L.dkt_instance_norm_stats(c.data_ptr(), ws.data_ptr(), planes, HW, dev, st), "dkt_instance_norm_stats")
-        rc = L.dkt_instance_norm_add_relu(a.data_ptr(), c.data_ptr(), out.data_ptr(), ws.data_ptr(), planes, HW, eps, dev, st)
-        _ffi.check(rc, "dkt_instance_norm_add_relu")
+        _ffi.call("dkt_instance_norm_stats", c, c.data_ptr(), ws.data_ptr(), planes, HW)
+        _ffi.call("dkt_instance_norm_add_relu", c, a.data_ptr(), c.data_ptr(), out.data_ptr(), ws.data_ptr(), planes, HW, eps)
         # `a` is not kept: the sign of the output carries the outer ReLU's mask
-        ctx.save_for_backward(c, out, _finalize(L, ws, planes, HW, eps, c))
+        ctx.save_for_backward(c, out, _finalize(ws, planes, HW, eps, c))
         return out
 
     @staticmethod
@@ -107,13 +98,11 @@ class _InstanceNormAddReluFn(torch.autograd.Function):
         gout = gout.contiguous()
         n, ch, h, w = c.shape
         planes, HW = n * ch, h * w
-        L = _ffi.lib()
         ga = torch.empty_like(c) if need_a else None
         gc = torch.empty_like(c) if need_c else None
-        ws = _bytes(L.dkt_instance_norm_bwd_workspace(planes, HW), c.device) if need_c else None
-        rc = L.dkt_instance_norm_add_relu_bwd(gout.data_ptr(), out.data_ptr(), c.data_ptr(), mi.data_ptr(), _ffi.ptr(ga),
-                                              _ffi.ptr(gc), _ffi.ptr(ws), planes, HW, _ffi.device_of(c), _ffi.stream_of(c))
-        _ffi.check(rc, "dkt_instance_norm_add_relu_bwd")
+        ws = _workspace("dkt_instance_norm_bwd_workspace", planes, HW, c.device) if need_c else None
+        _ffi.call("dkt_instance_norm_add_relu_bwd", c, gout.data_ptr(), out.data_ptr(), c.data_ptr(), mi.data_ptr(), _ffi.ptr(ga),
+                  _ffi.ptr(gc), _ffi.ptr(ws), planes, HW)
         return ga, gc, None
 
 

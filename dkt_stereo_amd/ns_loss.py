@@ -76,13 +76,9 @@ class _NsLoss(torch.autograd.Function):
             d.planes = planes.data_ptr()
         d.conf_threshold, d.max_flow, d.alpha_disp, d.alpha_photo = conf_threshold, max_flow, alpha_disp, alpha_photo
         d.loss, d.rec, d.B, d.H, d.W = loss.data_ptr(), rec.data_ptr(), B, H, W
-        L = _ffi.lib()
-        nbytes = L.dkt_ns_loss_workspace(B, H, W)
-        if nbytes < 0:
-            _ffi.check(nbytes, "dkt_ns_loss_workspace")
-        ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+        ws = torch.empty(_ffi.size("dkt_ns_loss_workspace", B, H, W) // 8, device=dev, dtype=torch.float64)
         with torch.cuda.device(dev):
-            _ffi.check(L.dkt_ns_loss(d, ws.data_ptr(), _ffi.device_of(ws), _ffi.stream_of(ws)), "dkt_ns_loss")
+            _ffi.call("dkt_ns_loss", ws, d, ws.data_ptr())
         ctx.desc, ctx.n = d, n
         ctx.set_materialize_grads(False)
         extra = [t for t in (valid, state, planes) if t is not None]
@@ -107,8 +103,7 @@ class _NsLoss(torch.autograd.Function):
             out.append(t)
             g.grad[i] = t.data_ptr()
         with torch.cuda.device(dev):
-            _ffi.check(_ffi.lib().dkt_ns_loss_bwd(ctx.desc, g, _ffi.device_of(preds[0]), _ffi.stream_of(preds[0])),
-                       "dkt_ns_loss_bwd")
+            _ffi.call("dkt_ns_loss_bwd", preds[0], ctx.desc, g)
         return (None,) * 6 + tuple(out)
 
 

@@ -43,10 +43,7 @@ _HYPER = ("lr", "betas", "eps", "weight_decay")
 
 
 def workspace_bytes(count, total):
-    n = _ffi.lib().dkt_adamw_workspace(int(count), int(total))
-    if n < 0:
-        raise _ffi.DktError("dkt_adamw_workspace rejected count=%d total=%d" % (count, total))
-    return n
+    return _ffi.size("dkt_adamw_workspace", int(count), int(total))
 
 
 def adamw_kernel(ps, gs, ms, vs, step, record, workspace, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=None,
@@ -60,11 +57,10 @@ def adamw_kernel(ps, gs, ms, vs, step, record, workspace, lr, betas=(0.9, 0.999)
     if workspace.numel() < workspace_bytes(len(ps), total):
         raise _ffi.DktError("dkt_adamw_step workspace too small")
     opt = lambda t: None if t is None else t.data_ptr()
-    rc = _ffi.lib().dkt_adamw_step(ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], len(ps), total, float(lr), float(betas[0]),
-                                   float(betas[1]), float(eps), float(weight_decay), -1.0 if max_norm is None else float(max_norm),
-                                   float(inv_scale), opt(grad_scale), opt(found_inf), step.data_ptr(), record.data_ptr(),
-                                   opt(absmax), workspace.data_ptr(), int(grid), _ffi.device_of(ps[0]), _ffi.stream_of(ps[0]))
-    _ffi.check(rc, "dkt_adamw_step")
+    _ffi.call("dkt_adamw_step", ps[0], ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], len(ps), total, float(lr), float(betas[0]),
+              float(betas[1]), float(eps), float(weight_decay), -1.0 if max_norm is None else float(max_norm),
+              float(inv_scale), opt(grad_scale), opt(found_inf), step.data_ptr(), record.data_ptr(),
+              opt(absmax), workspace.data_ptr(), int(grid))
 
 
 def _require(p):

@@ -30,15 +30,12 @@ class CorrBlock1D:
         self._w2 = w2
         lvl = corr.reshape(batch * h1 * w1, 1, 1, w2)
         self.corr_pyramid = [lvl]
-        L = _ffi.lib()
         for _ in range(num_levels - 1):
             w = lvl.shape[-1]
             if w // self.compress_factor < 1:
                 raise ValueError("width %d cannot be pooled by %d" % (w, self.compress_factor))
             nxt = torch.empty((lvl.shape[0], 1, 1, w // self.compress_factor), device=lvl.device, dtype=torch.float32)
-            rc = L.dkt_pool_rows(lvl.data_ptr(), nxt.data_ptr(), lvl.shape[0], w, self.compress_factor,
-                                 _ffi.device_of(lvl), _ffi.stream_of(lvl))
-            _ffi.check(rc, "dkt_pool_rows")
+            _ffi.call("dkt_pool_rows", lvl, lvl.data_ptr(), nxt.data_ptr(), lvl.shape[0], w, self.compress_factor)
             self.corr_pyramid.append(nxt)
             lvl = nxt
 
@@ -52,10 +49,8 @@ class CorrBlock1D:
         B, G, H, W1 = coords.shape
         Lv, S = self.num_levels, self.sample_num
         out = torch.empty((B, Lv * G * S, H, W1), device=coords.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_pcv_lookup(_ffi.ptr_array(self.corr_pyramid), coords.data_ptr(), sigma.data_ptr(),
-                                       out.data_ptr(), B, G, H, W1, self._w2, Lv, S, self.compress_factor,
-                                       _ffi.device_of(coords), _ffi.stream_of(coords))
-        _ffi.check(rc, "dkt_pcv_lookup")
+        _ffi.call("dkt_pcv_lookup", coords, _ffi.ptr_array(self.corr_pyramid), coords.data_ptr(), sigma.data_ptr(),
+                  out.data_ptr(), B, G, H, W1, self._w2, Lv, S, self.compress_factor)
         return out
 
     @staticmethod

@@ -369,9 +369,8 @@ class RAFTStereo(nn.Module):
             a = image1 if image1[0].is_contiguous() else image1.contiguous()
             b = image2 if image2[0].is_contiguous() else image2.contiguous()
             both = torch.empty((2 * B,) + tuple(image1.shape[1:]), device=image1.device, dtype=torch.float32)
-            rc = _ffi.lib().dkt_normalize_pair(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), both.data_ptr(), B,
-                                               a[0].numel(), _ffi.device_of(a), _ffi.stream_of(a))
-            _ffi.check(rc, "dkt_normalize_pair")
+            _ffi.call("dkt_normalize_pair", a, a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), both.data_ptr(), B,
+                      a[0].numel())
             return both[:B], both[B:], both
         image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
         image2 = (2 * (image2 / 255.0) - 1.0).contiguous()
@@ -483,9 +482,7 @@ class RAFTStereo(nn.Module):
             flow = flow.float().contiguous()
             mask = mask.float().contiguous()
             out = torch.empty((N, D, factor * H, factor * W), device=flow.device, dtype=torch.float32)
-            rc = _ffi.lib().dkt_convex_upsample(flow.data_ptr(), mask.data_ptr(), out.data_ptr(), N, D, H, W,
-                                                factor, _ffi.device_of(flow), _ffi.stream_of(flow))
-            _ffi.check(rc, "dkt_convex_upsample")
+            _ffi.call("dkt_convex_upsample", flow, flow.data_ptr(), mask.data_ptr(), out.data_ptr(), N, D, H, W, factor)
             return out
         mask = torch.softmax(mask.view(N, 1, 9, factor, factor, H, W), dim=2)
         up = F.unfold(factor * flow, [3, 3], padding=1).view(N, D, 9, 1, 1, H, W)

@@ -25,9 +25,7 @@ def _batch_strided(t):
 def _forward(cost, bstride, factor, out_scale):
     B, D, h, w = cost.shape
     out = torch.empty((B, 1, factor * h, factor * w), device=cost.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_soft_argmin_fwd(cost.data_ptr(), bstride, out_scale, out.data_ptr(), B, D, h, w, factor,
-                                        _ffi.device_of(cost), _ffi.stream_of(cost))
-    _ffi.check(rc, "dkt_soft_argmin_fwd")
+    _ffi.call("dkt_soft_argmin_fwd", cost, cost.data_ptr(), bstride, out_scale, out.data_ptr(), B, D, h, w, factor)
     return out
 
 
@@ -48,15 +46,11 @@ class _SoftArgminFn(torch.autograd.Function):
         B, D, h, w = cost.shape
         _ffi.require_gpu(gout)
         g, gbs = _batch_strided(gout)
-        lib = _ffi.lib()
-        nbytes = lib.dkt_soft_argmin_bwd_workspace(B, D, h, w, ctx.factor)
-        if nbytes < 0:
-            _ffi.check(nbytes, "dkt_soft_argmin_bwd_workspace")
+        nbytes = _ffi.size("dkt_soft_argmin_bwd_workspace", B, D, h, w, ctx.factor)
         ws = torch.empty(nbytes // 4, device=cost.device, dtype=torch.float32) if nbytes else None
         gcost = torch.empty((B, D, h, w), device=cost.device, dtype=torch.float32)
-        rc = lib.dkt_soft_argmin_bwd(g.data_ptr(), gbs, cost.data_ptr(), ctx.bstride, ctx.out_scale, gcost.data_ptr(), _ffi.ptr(ws),
-                                     B, D, h, w, ctx.factor, _ffi.device_of(cost), _ffi.stream_of(cost))
-        _ffi.check(rc, "dkt_soft_argmin_bwd")
+        _ffi.call("dkt_soft_argmin_bwd", cost, g.data_ptr(), gbs, cost.data_ptr(), ctx.bstride, ctx.out_scale, gcost.data_ptr(),
+                  _ffi.ptr(ws), B, D, h, w, ctx.factor)
         return gcost, None, None
 
 

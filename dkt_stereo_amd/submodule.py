@@ -54,23 +54,17 @@ def _gwc_into(ref, tgt, vol, maxdisp, num_groups, bstride):
     B, C, H, W = ref.shape
     assert C % num_groups == 0  # groupwise_correlation, submodule.py:154
     if GWC_MODE == "mfma":
-        rc = _ffi.lib().dkt_gwc_volume_mfma(ref.data_ptr(), tgt.data_ptr(), vol.data_ptr(), B, C, H, W,
-                                            maxdisp, num_groups, bstride, _ffi.device_of(ref), _ffi.stream_of(ref))
-        if rc == 0:
+        # E_UNSUPPORTED: shape outside the MFMA form -> the general kernel
+        if _ffi.call("dkt_gwc_volume_mfma", ref, ref.data_ptr(), tgt.data_ptr(), vol.data_ptr(), B, C, H, W,
+                     maxdisp, num_groups, bstride, ok=(_ffi.E_UNSUPPORTED,)) == 0:
             return
-        if rc != -7:                              # DKT_E_UNSUPPORTED: shape outside the MFMA form -> the general kernel
-            _ffi.check(rc, "dkt_gwc_volume_mfma")
-    rc = _ffi.lib().dkt_gwc_volume(ref.data_ptr(), tgt.data_ptr(), vol.data_ptr(), B, C, H, W,
-                                   maxdisp, num_groups, bstride, _ffi.device_of(ref), _ffi.stream_of(ref))
-    _ffi.check(rc, "dkt_gwc_volume")
+    _ffi.call("dkt_gwc_volume", ref, ref.data_ptr(), tgt.data_ptr(), vol.data_ptr(), B, C, H, W, maxdisp, num_groups, bstride)
 
 
 def _concat_into(ref, tgt, vol, maxdisp, ref_masked, bstride):
     B, C, H, W = ref.shape
-    rc = _ffi.lib().dkt_concat_volume(ref.data_ptr(), tgt.data_ptr(), vol.data_ptr(), B, C, H, W,
-                                      maxdisp, int(ref_masked), bstride,
-                                      _ffi.device_of(ref), _ffi.stream_of(ref))
-    _ffi.check(rc, "dkt_concat_volume")
+    _ffi.call("dkt_concat_volume", ref, ref.data_ptr(), tgt.data_ptr(), vol.data_ptr(), B, C, H, W,
+              maxdisp, int(ref_masked), bstride)
 
 
 def _gwc_volume(ref, tgt, maxdisp, num_groups):
@@ -135,9 +129,8 @@ class _GwcFn(torch.autograd.Function):
         gt = _empty_or_none(ctx.needs_input_grad[1], tgt)
         if gr is None and gt is None:
             return None, None, None, None
-        rc = _ffi.lib().dkt_gwc_volume_bwd(gv.data_ptr(), bstride, ref.data_ptr(), tgt.data_ptr(), _ffi.ptr(gr), _ffi.ptr(gt),
-                                           B, C, H, W, D, G, _ffi.device_of(ref), _ffi.stream_of(ref))
-        _ffi.check(rc, "dkt_gwc_volume_bwd")
+        _ffi.call("dkt_gwc_volume_bwd", ref, gv.data_ptr(), bstride, ref.data_ptr(), tgt.data_ptr(), _ffi.ptr(gr), _ffi.ptr(gt),
+                  B, C, H, W, D, G)
         return gr, gt, None, None
 
 
@@ -159,9 +152,7 @@ class _ConcatFn(torch.autograd.Function):
         gr, gt = mk(ctx.needs_input_grad[0]), mk(ctx.needs_input_grad[1])
         if gr is None and gt is None:
             return None, None, None, None
-        rc = _ffi.lib().dkt_concat_volume_bwd(gv.data_ptr(), bstride, _ffi.ptr(gr), _ffi.ptr(gt), B, C, H, W, D, int(ref_masked),
-                                              _ffi.device_of(gv), _ffi.stream_of(gv))
-        _ffi.check(rc, "dkt_concat_volume_bwd")
+        _ffi.call("dkt_concat_volume_bwd", gv, gv.data_ptr(), bstride, _ffi.ptr(gr), _ffi.ptr(gt), B, C, H, W, D, int(ref_masked))
         return gr, gt, None, None
 
 
@@ -189,10 +180,8 @@ class _GwcConcatFn(torch.autograd.Function):
         cr, ct = mk(need[2]), mk(need[3])
         if gr is None and gt is None and cr is None and ct is None:
             return None, None, None, None, None, None
-        rc = _ffi.lib().dkt_gwc_concat_volume_bwd(gv.data_ptr(), bstride, gref.data_ptr(), gtgt.data_ptr(), _ffi.ptr(gr), _ffi.ptr(gt),
-                                                  B, C, G, _ffi.ptr(cr), _ffi.ptr(ct), Cc, 1, H, W, D,
-                                                  _ffi.device_of(gv), _ffi.stream_of(gv))
-        _ffi.check(rc, "dkt_gwc_concat_volume_bwd")
+        _ffi.call("dkt_gwc_concat_volume_bwd", gv, gv.data_ptr(), bstride, gref.data_ptr(), gtgt.data_ptr(), _ffi.ptr(gr),
+                  _ffi.ptr(gt), B, C, G, _ffi.ptr(cr), _ffi.ptr(ct), Cc, 1, H, W, D)
         return gr, gt, cr, ct, None, None
 
 
@@ -236,9 +225,7 @@ def _group_l2norm(x, num_groups):
     if C % num_groups != 0:
         raise AssertionError("C %% num_groups != 0")          # the reference asserts (submodule.py:145)
     y = torch.empty_like(x)
-    rc = _ffi.lib().dkt_group_l2norm(x.data_ptr(), y.data_ptr(), B, C, H * W, num_groups, 1e-05,
-                                     _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_group_l2norm")
+    _ffi.call("dkt_group_l2norm", x, x.data_ptr(), y.data_ptr(), B, C, H * W, num_groups, 1e-05)
     return y
 
 

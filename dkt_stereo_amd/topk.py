@@ -19,9 +19,8 @@ MAX_D = 256
 def _forward(cost, cbs, samples, sbs, k, idx=None):
     B, D, h, w = cost.shape
     out = torch.empty((B, 1, h, w), device=cost.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_topk_regress_fwd(cost.data_ptr(), cbs, _ffi.ptr(samples), sbs, out.data_ptr(), _ffi.ptr(idx), B, D, h, w, k,
-                                         _ffi.device_of(cost), _ffi.stream_of(cost))
-    _ffi.check(rc, "dkt_topk_regress_fwd")
+    _ffi.call("dkt_topk_regress_fwd", cost, cost.data_ptr(), cbs, _ffi.ptr(samples), sbs, out.data_ptr(), _ffi.ptr(idx),
+              B, D, h, w, k)
     return out
 
 
@@ -51,10 +50,8 @@ class _TopkRegressFn(torch.autograd.Function):
         g, gbs = _batch_strided(gout)
         gcost = torch.empty((B, D, h, w), device=cost.device, dtype=torch.float32) if need_cost else None
         gsamples = torch.empty((B, D, h, w), device=cost.device, dtype=torch.float32) if need_samples else None
-        rc = _ffi.lib().dkt_topk_regress_bwd(g.data_ptr(), gbs, cost.data_ptr(), ctx.cbs, _ffi.ptr(samples), ctx.sbs, idx.data_ptr(),
-                                             _ffi.ptr(gcost), _ffi.ptr(gsamples), B, D, h, w, ctx.k,
-                                             _ffi.device_of(cost), _ffi.stream_of(cost))
-        _ffi.check(rc, "dkt_topk_regress_bwd")
+        _ffi.call("dkt_topk_regress_bwd", cost, g.data_ptr(), gbs, cost.data_ptr(), ctx.cbs, _ffi.ptr(samples), ctx.sbs,
+                  idx.data_ptr(), _ffi.ptr(gcost), _ffi.ptr(gsamples), B, D, h, w, ctx.k)
         return gcost, gsamples, None
 
 

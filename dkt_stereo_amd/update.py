@@ -317,8 +317,6 @@ class ConvGRU(nn.Module):
         _ffi.require_no_grad(h, cz, cr, cq, *x_list)
         B, Ch, H, W = h.shape
         HW = H * W
-        L = _ffi.lib()
-        dev, st = _ffi.device_of(h), _ffi.stream_of(h)
         if not _batch_dense(h, HW):
             h = h.contiguous()
         cz, cr, cq = [t if _batch_dense(t, HW) else t.contiguous() for t in (cz, cr, cq)]
@@ -342,19 +340,15 @@ class ConvGRU(nn.Module):
         _ffi.require_gpu(azr)        # fp32 only: under torch.autocast the vendor conv returns half
         z = torch.empty((B, Ch, H, W), device=h.device, dtype=torch.float32)
         # z = sigmoid(az+cz); r = sigmoid(ar+cr); rh <- r*h
-        rc = L.dkt_gru_gate_zr(azr.data_ptr(), cz.data_ptr(), cz.stride(0), cr.data_ptr(), cr.stride(0),
-                               h.data_ptr(), h.stride(0), z.data_ptr(), rh.data_ptr(), rh.stride(0),
-                               B, Ch, HW, dev, st)
-        _ffi.check(rc, "dkt_gru_gate_zr")
+        _ffi.call("dkt_gru_gate_zr", h, azr.data_ptr(), cz.data_ptr(), cz.stride(0), cr.data_ptr(), cr.stride(0),
+                  h.data_ptr(), h.stride(0), z.data_ptr(), rh.data_ptr(), rh.stride(0), B, Ch, HW)
         aq = conv2d(q_in, self.convq)
         _ffi.require_gpu(aq)
         if out is None:
             out = torch.empty((B, Ch, H, W), device=h.device, dtype=torch.float32)
         # q = tanh(aq+cq); h' = (1-z)*h + z*q
-        rc = L.dkt_gru_gate_out(aq.data_ptr(), cq.data_ptr(), cq.stride(0), z.data_ptr(),
-                                h.data_ptr(), h.stride(0), out.data_ptr(), out.stride(0),
-                                B, Ch, HW, dev, st)
-        _ffi.check(rc, "dkt_gru_gate_out")
+        _ffi.call("dkt_gru_gate_out", h, aq.data_ptr(), cq.data_ptr(), cq.stride(0), z.data_ptr(),
+                  h.data_ptr(), h.stride(0), out.data_ptr(), out.stride(0), B, Ch, HW)
         return out
 
 
@@ -484,8 +478,7 @@ def pool2x(x):
     x = x.contiguous()
     B, C, H, W = x.shape
     y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), device=x.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_pool2x(x.data_ptr(), y.data_ptr(), B * C, H, W, _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_pool2x")
+    _ffi.call("dkt_pool2x", x, x.data_ptr(), y.data_ptr(), B * C, H, W)
     return y
 
 
@@ -497,9 +490,7 @@ def interp(x, dest):
     B, C, H, W = x.shape
     Ho, Wo = dest.shape[2:]
     y = torch.empty((B, C, Ho, Wo), device=x.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_interp_bilinear(x.data_ptr(), y.data_ptr(), B * C, H, W, Ho, Wo,
-                                        _ffi.device_of(x), _ffi.stream_of(x))
-    _ffi.check(rc, "dkt_interp_bilinear")
+    _ffi.call("dkt_interp_bilinear", x, x.data_ptr(), y.data_ptr(), B * C, H, W, Ho, Wo)
     return y
 
 

@@ -36,9 +36,8 @@ def _backward(name, gout, coarse, nine, needs, channels, dims, scale=()):
     gcoarse = torch.empty_like(coarse) if need_coarse else None
     gnine = torch.empty_like(nine) if need_nine else None
     ws = torch.empty((N, channels, 9, H, W), device=coarse.device, dtype=torch.float32) if need_coarse else None
-    rc = getattr(_ffi.lib(), name)(g.data_ptr(), bstride, coarse.data_ptr(), nine.data_ptr(), *scale, _ffi.ptr(gcoarse),
-                                   _ffi.ptr(gnine), _ffi.ptr(ws), *dims, _ffi.device_of(g), _ffi.stream_of(g))
-    _ffi.check(rc, name)
+    _ffi.call(name, g, g.data_ptr(), bstride, coarse.data_ptr(), nine.data_ptr(), *scale, _ffi.ptr(gcoarse),
+              _ffi.ptr(gnine), _ffi.ptr(ws), *dims)
     return gcoarse, gnine
 
 
@@ -51,9 +50,7 @@ class _ConvexUpsampleFn(torch.autograd.Function):
             raise _ffi.DktError("upsample mask %s does not match flow %s at factor %d" % (tuple(mask.shape), tuple(flow.shape), factor))
         flow, mask = flow.contiguous(), mask.contiguous()
         out = torch.empty((N, channels, factor * H, factor * W), device=flow.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_convex_upsample_fwd(flow.data_ptr(), mask.data_ptr(), out.data_ptr(), N, D, channels, H, W, factor,
-                                                _ffi.device_of(flow), _ffi.stream_of(flow))
-        _ffi.check(rc, "dkt_convex_upsample_fwd")
+        _ffi.call("dkt_convex_upsample_fwd", flow, flow.data_ptr(), mask.data_ptr(), out.data_ptr(), N, D, channels, H, W, factor)
         ctx.save_for_backward(flow, mask)
         ctx.factor, ctx.channels = factor, channels
         return out
@@ -85,9 +82,7 @@ def _context_upsample(disp_low, up_weights):
     """dkt_context_upsample on fp32 contiguous tensors."""
     b, _, h, w = disp_low.shape
     out = torch.empty((b, 4 * h, 4 * w), device=disp_low.device, dtype=torch.float32)
-    rc = _ffi.lib().dkt_context_upsample(disp_low.data_ptr(), up_weights.data_ptr(), out.data_ptr(), b, h, w,
-                                         _ffi.device_of(out), _ffi.stream_of(out))
-    _ffi.check(rc, "dkt_context_upsample")
+    _ffi.call("dkt_context_upsample", out, disp_low.data_ptr(), up_weights.data_ptr(), out.data_ptr(), b, h, w)
     return out
 
 
@@ -122,9 +117,7 @@ class _ContextUpsampleLogitsFn(torch.autograd.Function):
     def forward(ctx, disp_low, logits, scale):
         B, _, h, w = disp_low.shape
         out = torch.empty((B, 4 * h, 4 * w), device=disp_low.device, dtype=torch.float32)
-        rc = _ffi.lib().dkt_context_upsample_logits_fwd(disp_low.data_ptr(), logits.data_ptr(), scale, out.data_ptr(), B, h, w,
-                                                        _ffi.device_of(out), _ffi.stream_of(out))
-        _ffi.check(rc, "dkt_context_upsample_logits_fwd")
+        _ffi.call("dkt_context_upsample_logits_fwd", out, disp_low.data_ptr(), logits.data_ptr(), scale, out.data_ptr(), B, h, w)
         ctx.save_for_backward(disp_low, logits)
         ctx.scale = scale
         return out

@@ -2,82 +2,21 @@
 launch, _ffi.SIGNATURES matches the header's declarations, the GRAD_PREPASS handle, and conv2d_autograd(..., owner=) on CPU
 tensors, which stays plain torch."""
 import ctypes
-import os
-import re
 
 import torch
 import torch.nn as nn
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import _abi_header
+
 NAMES = ["dkt_conv_grad_prepass_ws_floats", "dkt_conv_grad_prepass"]
-_CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}
 
 
-def _declared(name):
-    """(return type, [argument ctypes]) of `name` as include/dktstereo.h declares it."""
-    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\b(int|long)\s+%s\s*\(([^;]*?)\)\s*;" % name, hdr, flags=re.S)
-    assert m, name
-    args = []
-    for a in m.group(2).split(","):
-        a = " ".join(a.split())
-        if "*const *" in a or "* const *" in a:
-            args.append(ctypes.POINTER(ctypes.c_void_p))
-        elif "*" in a:
-            base = a.replace("const", "").split("*")[0].strip()
-            args.append({"int": ctypes.POINTER(ctypes.c_int), "long": ctypes.POINTER(ctypes.c_long)}.get(base, ctypes.c_void_p))
-        else:
-            args.append(_CTYPES[a.split()[0]])
-    return m.group(1), args
-
-
-def _declared_struct(name):
-    """[(field, ctype)] of `typedef struct name { ... } name;` as include/dktstereo.h declares it: pointers as c_void_p,
-    arrays by the header's own #define of their length."""
-    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    consts = {k: int(v) for k, v in re.findall(r"#define\s+(\w+)\s+(\d+)\s*$", hdr, flags=re.M)}
-    m = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (name, name), hdr, flags=re.S)
-    assert m, name
-    fields = []
-    for decl in m.group(1).split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        base = re.match(r"(?:const )?(void|float|int|long)\b", decl)
-        assert base, decl
-        for item in decl[base.end():].split(","):
-            star, field, dim = re.match(r"\s*(\*?)\s*(\w+)(?:\[(\w+)\])?\s*$", item).groups()
-            ct = ctypes.c_void_p if star else _CTYPES[base.group(1)]
-            fields.append((field, ct * (consts[dim] if dim in consts else int(dim)) if dim else ct))
-    return fields
-
-
-def test_conv_desc_mirrors_the_header():
-    """_ffi.ConvDesc is dkt_conv_desc field for field -- names, order, array lengths, C types: every dkt_conv2d_f16s launch
-    goes through that mirror."""
-    from dkt_stereo_amd import _ffi
-    want = _declared_struct("dkt_conv_desc")
-    got = list(_ffi.ConvDesc._fields_)
-    assert [n for n, _ in got] == [n for n, _ in want]
-
-    def shape(t):
-        return (t._type_, t._length_) if issubclass(t, ctypes.Array) else (t, 0)
-    assert [shape(t) for _, t in got] == [shape(t) for _, t in want]
-    assert want[-1] == ("dscale", ctypes.c_void_p) and shape(want[0][1]) == (ctypes.c_void_p, 4)
-
-
-def test_signatures_match_the_header():
-    from dkt_stereo_amd import _ffi
-    lib = _ffi.lib()
-    for name in NAMES:
-        ret, args = _declared(name)
-        assert _ffi.SIGNATURES[name] == args, name
-        assert _ffi.RESTYPES.get(name, ctypes.c_int) is (ctypes.c_long if ret == "long" else ctypes.c_int), name
-        assert hasattr(lib, name)
-    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
-    assert re.search(r"#define\s+DKT_CONV_GRAD_MAX_EXP\s+80\b", hdr)
+def test_header_facts():
+    """dkt_conv_desc ends with the device scale and opens with its four operand pointers (the whole struct against _ffi.ConvDesc:
+    test_host_abi_mirror.py); the exponent clamp of the pre-pass."""
+    want = _abi_header.structs()["dkt_conv_desc"]
+    assert want[-1] == ("dscale", ctypes.c_void_p, 0) and want[0] == ("src", ctypes.c_void_p, 4)
+    assert _abi_header.defines()["DKT_CONV_GRAD_MAX_EXP"] == 80
 
 
 def test_entries_refuse_bad_arguments_before_launch():

@@ -3,45 +3,17 @@ header's declarations; every argument error returns its code before any device i
 untouched); the workspace size is positive, monotone and follows the plan _conv_s2_ref restates; conv2d_autograd on a CPU
 stride-2 layer and extractor._Conv2d under autograd on the CPU -- handle off and on -- stay plain torch."""
 import ctypes
-import os
-import re
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import _abi_header
 import _conv_s2_ref as S
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-NAMES = ["dkt_conv2d_dgrad_s2", "dkt_conv2d_wgrad_s2_ws_floats", "dkt_conv2d_wgrad_s2"]
-_CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}
 
-
-def _header():
-    return open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
-
-
-def _declared(name):
-    """(return type, [argument ctypes]) of `name` as include/dktstereo.h declares it."""
-    hdr = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\b(int|long)\s+%s\s*\(([^;]*?)\)\s*;" % name, hdr, flags=re.S)
-    assert m, name
-    args = []
-    for a in m.group(2).split(","):
-        a = " ".join(a.split())
-        args.append(ctypes.c_void_p if "*" in a else _CTYPES[a.split()[0]])
-    return m.group(1), args
-
-
-def test_signatures_match_the_header():
-    from dkt_stereo_amd import _ffi
-    lib = _ffi.lib()
-    for name in NAMES:
-        ret, args = _declared(name)
-        assert _ffi.SIGNATURES[name] == args, name
-        assert _ffi.RESTYPES.get(name, ctypes.c_int) is (ctypes.c_long if ret == "long" else ctypes.c_int), name
-        assert hasattr(lib, name)
-    hdr = _header()
+def test_header_cites_the_reference():
+    hdr = _abi_header.raw()
     block = hdr[hdr.index("backward of the encoders' stride-2 convolutions"):hdr.index("int dkt_conv2d_dgrad_s2")]
     assert "core/extractor.py:6-60, :122-175" in block
 

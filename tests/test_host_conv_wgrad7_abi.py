@@ -3,18 +3,13 @@ _ffi.SIGNATURES matches the header's declarations, the workspace sizes are the r
 _conv_wgrad7_ref.py restates, the GRAD_WEIGHT7_HIP handle is off, and conv2d_autograd on CPU tensors stays plain torch with
 the handle on."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 import torch.nn as nn
 
+import _abi_header
 import _conv_wgrad7_ref as W7
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-NAMES = ["dkt_conv2d_wgrad7_ws_floats", "dkt_conv2d_wgrad7"]
-_CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}
 
 #: (B, H, W, Cin, Cout): dkt_conv2d_wgrad7_ws_floats, recorded by hand from the rule (slices * Cout * Cin * 49)
 TABLE = {
@@ -40,28 +35,8 @@ TABLE = {
 }
 
 
-def _declared(name):
-    """(return type, [argument ctypes]) of `name` as include/dktstereo.h declares it."""
-    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\b(int|long)\s+%s\s*\(([^;]*?)\)\s*;" % name, hdr, flags=re.S)
-    assert m, name
-    args = []
-    for a in m.group(2).split(","):
-        a = " ".join(a.split())
-        args.append(ctypes.c_void_p if "*" in a else _CTYPES[a.split()[0]])
-    return m.group(1), args
-
-
-def test_signatures_match_the_header():
-    from dkt_stereo_amd import _ffi
-    lib = _ffi.lib()
-    for name in NAMES:
-        ret, args = _declared(name)
-        assert _ffi.SIGNATURES[name] == args, name
-        assert _ffi.RESTYPES.get(name, ctypes.c_int) is (ctypes.c_long if ret == "long" else ctypes.c_int), name
-        assert hasattr(lib, name)
-    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
+def test_header_cites_the_reference():
+    hdr = _abi_header.raw()
     block = hdr[hdr.index("weight gradient of the 7x7 stem layers"):hdr.index("long dkt_conv2d_wgrad7_ws_floats")]
     for cite in ("core/extractor.py:140, :217", "core/update.py:73", "igev_stereo/update.py:80"):
         assert cite in block, cite

@@ -2,41 +2,16 @@
 workspace size follows the slice rule _conv_wgrad_ref.plan restates, _ffi.SIGNATURES matches the header's declarations, the
 GRAD_WEIGHT_HIP handle, and conv2d_autograd on CPU tensors, which stays plain torch."""
 import ctypes
-import os
-import re
 
 import torch
 import torch.nn as nn
 
+import _abi_header
 import _conv_wgrad_ref as WR
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-NAMES = ["dkt_conv2d_wgrad_ws_floats", "dkt_conv2d_wgrad"]
-_CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}
 
-
-def _declared(name):
-    """(return type, [argument ctypes]) of `name` as include/dktstereo.h declares it."""
-    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\b(int|long)\s+%s\s*\(([^;]*?)\)\s*;" % name, hdr, flags=re.S)
-    assert m, name
-    args = []
-    for a in m.group(2).split(","):
-        a = " ".join(a.split())
-        args.append(ctypes.c_void_p if "*" in a else _CTYPES[a.split()[0]])
-    return m.group(1), args
-
-
-def test_signatures_match_the_header():
-    from dkt_stereo_amd import _ffi
-    lib = _ffi.lib()
-    for name in NAMES:
-        ret, args = _declared(name)
-        assert _ffi.SIGNATURES[name] == args, name
-        assert _ffi.RESTYPES.get(name, ctypes.c_int) is (ctypes.c_long if ret == "long" else ctypes.c_int), name
-        assert hasattr(lib, name)
-    hdr = open(os.path.join(HERE, "..", "include", "dktstereo.h")).read()
+def test_header_cites_the_reference():
+    hdr = _abi_header.raw()
     block = hdr[hdr.index("/* dkt_conv2d_wgrad:"):hdr.index("long dkt_conv2d_wgrad_ws_floats")]
     assert "core/update.py:9-10, 19-21, 72-76, 111-113" in block
 

@@ -2,16 +2,14 @@
 the header's declarations against _ffi.SIGNATURES, the nodes' refusal of CPU tensors, and the CPU encoder under autograd,
 which stays on torch whatever extractor.TRAIN_NORM_NODES says."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import _abi_header
 import _encoder_ref as er
 import _norm_train_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dkt_instance_norm_bwd_workspace", "dkt_instance_norm_bwd", "dkt_instance_norm_add_relu_bwd")
 
 
@@ -49,23 +47,8 @@ def test_entries_refuse_bad_arguments_before_launch():
     assert all(v == 0.0 for v in buf)                                   # nothing was written
 
 
-def _ctype(decl):
-    if "*" in decl:
-        return ctypes.c_void_p
-    return {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float}[decl.replace("const", "").split()[0]]
-
-
-def test_header_matches_the_signatures():
-    from dkt_stereo_amd import _ffi
-    hdr = open(os.path.join(ROOT, "include", "dktstereo.h")).read()
-    for name in NAMES:
-        m = re.search(r"\b(int|long)\s+%s\s*\((.*?)\)\s*;" % name, hdr, re.S)
-        assert m, name
-        params = [a for a in re.sub(r"/\*.*?\*/", "", m.group(2), flags=re.S).split(",")]
-        assert [_ctype(a) for a in params] == _ffi.SIGNATURES[name], name
-        assert _ffi.RESTYPES.get(name, ctypes.c_int) is {"int": ctypes.c_int, "long": ctypes.c_long}[m.group(1)], name
-        assert hasattr(_ffi.lib(), name)
-    # each cites the reference lines it replaces
+def test_header_cites_the_reference():
+    hdr = _abi_header.raw()
     doc = hdr[:hdr.index("long dkt_instance_norm_bwd_workspace")]
     assert "core/extractor.py:21-33" in doc[-1800:] and "core/extractor.py:52-60" in doc[-1800:]
 

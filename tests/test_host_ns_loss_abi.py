@@ -1,31 +1,20 @@
 """The C ABI of the NeRF-supervised loss without a device: the symbols, the header against _ffi, every argument error before
 any device call, the workspace table, and the Python entry points' refusals."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
+import _abi_header
 from dkt_stereo_amd import _ffi, loss, ns_loss as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NULL, SHAPE, ALIGN, UNSUPPORTED = -1, -2, -6, -7
 
 
-def test_symbols_and_header():
-    lib = _ffi.lib()
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dktstereo.h")).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(dkt_ns_[a-z0-9_]+)\s*\(", hdr)))
+def test_header_declares_the_three_entries():
+    """(their signatures, the struct and the constants against _ffi: test_host_abi_mirror.py)"""
+    declared = sorted(n for n in _abi_header.functions() if n.startswith("dkt_ns_"))
     assert declared == ["dkt_ns_loss", "dkt_ns_loss_bwd", "dkt_ns_loss_workspace"]
-    for name in declared:
-        assert hasattr(lib, name) and name in _ffi.SIGNATURES
-    assert _ffi.RESTYPES["dkt_ns_loss_workspace"] is ctypes.c_long
-    assert "#define DKT_NS_MAX_PRED %d" % _ffi.NS_MAX_PRED in hdr and "#define DKT_NS_REC %d" % _ffi.NS_REC in hdr
-    # the struct's fields in the header's order
-    body = re.search(r"typedef struct dkt_ns_loss_desc \{(.*?)\} dkt_ns_loss_desc;", hdr, re.S).group(1)
-    names = re.findall(r"[\s\*]([A-Za-z_][A-Za-z_0-9]*)(?:\[\w+\])?\s*[;,]", body)
-    assert names == [f[0] for f in _ffi.NsLossDesc._fields_]
 
 
 class _Host:

@@ -3,42 +3,11 @@ _ffi.SIGNATURES, the argument errors (negative DKT_E_* before any device call), 
 parameters the kernel cannot take."""
 import ctypes
 import math
-import os
-import re
 
 import pytest
 import torch
 
 DKT_OK, DKT_E_NULL, DKT_E_SHAPE, DKT_E_UNSUPPORTED = 0, -1, -2, -7
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("dkt_adamw_workspace", "dkt_adamw_step")
-
-
-def _declared(name):
-    """(restype, [argtypes]) of `name` as include/dktstereo.h declares it."""
-    hdr = open(os.path.join(ROOT, "include", "dktstereo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\b(int|long)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-    assert m, name
-
-    def ctype(arg):
-        if "*" in arg:
-            return ctypes.c_void_p
-        for word, t in (("double", ctypes.c_double), ("float", ctypes.c_float), ("long", ctypes.c_long), ("int", ctypes.c_int)):
-            if re.search(r"\b%s\b" % word, arg):
-                return t
-        raise AssertionError(arg)
-    return {"int": ctypes.c_int, "long": ctypes.c_long}[m.group(1)], [ctype(a) for a in m.group(2).split(",")]
-
-
-def test_symbols_and_declarations():
-    from dkt_stereo_amd import _ffi
-    lib = _ffi.lib()
-    for name in NAMES:
-        assert hasattr(lib, name)
-        restype, argtypes = _declared(name)
-        assert _ffi.SIGNATURES[name] == argtypes, name
-        assert _ffi.RESTYPES.get(name, ctypes.c_int) == restype, name
 
 
 def _call(lib, **kw):

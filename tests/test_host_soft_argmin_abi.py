@@ -2,41 +2,12 @@
 _ffi.SIGNATURES, their argument errors before any device call, the workspace rule on a literal table, the refusal of CPU
 tensors, and GWCNet's handle with the torch lines still behind it on the CPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {"dkt_soft_argmin_fwd": "int", "dkt_soft_argmin_bwd": "int", "dkt_soft_argmin_bwd_workspace": "long"}
 E_NULL, E_SHAPE, E_ALIGN, E_UNSUPPORTED = -1, -2, -6, -7
-
-
-def _declared(name, restype):
-    """[argtypes] of `name` as include/dktstereo.h declares it."""
-    hdr = open(os.path.join(ROOT, "include", "dktstereo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\b%s\s+%s\s*\(([^)]*)\)\s*;" % (restype, name), hdr)
-    assert m, name
-
-    def ctype(arg):
-        if "*" in arg:
-            return ctypes.c_void_p
-        for word, t in (("float", ctypes.c_float), ("long", ctypes.c_long), ("int", ctypes.c_int)):
-            if re.search(r"\b%s\b" % word, arg):
-                return t
-        raise AssertionError(arg)
-    return [ctype(a) for a in m.group(1).split(",")]
-
-
-def test_symbols_and_declarations():
-    from dkt_stereo_amd import _ffi
-    lib = _ffi.lib()
-    for name, restype in NAMES.items():
-        assert hasattr(lib, name), name
-        assert _ffi.SIGNATURES[name] == _declared(name, restype), name
-        assert _ffi.RESTYPES.get(name, ctypes.c_int) is (ctypes.c_long if restype == "long" else ctypes.c_int), name
 
 
 def test_entries_refuse_bad_arguments_before_any_device_call():

@@ -71,26 +71,7 @@ def test_no_cpu_fallback():
             build_gwc_volume(f, f, 2, 2)
 
 
-# ---- C ABI -----------------------------------------------------------------------
-def declared_symbols():
-    hdr = open(os.path.join(ROOT, "include", "dktstereo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return sorted(set(re.findall(r"\b(dkt_[a-z0-9_]+)\s*\(", hdr)))
-
-
-def test_abi_exports_every_declared_symbol():
-    from dkt_stereo_amd import _ffi
-    lib = _ffi.lib()
-    names = declared_symbols()
-    assert len(names) >= 13
-    for n in names:
-        assert hasattr(lib, n), n
-    assert set(_ffi.SIGNATURES) | {"dkt_version", "dkt_strerror"} == set(names)
-    assert lib.dkt_version() == 1
-    assert lib.dkt_strerror(0) == b"ok"
-    assert b"null" in lib.dkt_strerror(-1)
-
-
+# ---- C ABI (the surface and its ctypes mirror: test_host_abi_mirror.py) --------------
 def test_abi_argument_errors_before_launch():
     """Host-side validation returns negative codes without touching a device."""
     from dkt_stereo_amd import _ffi
