@@ -70,6 +70,16 @@ def _skew_pyramid(pyramid, B, H, W1, W2, out=None):
     return out
 
 
+def _volume_grads(gvol, f1, f2, need1, need2):
+    """The two products that carry the gradient of the all-pairs volume, gvol (B*H*W1, W2), to the feature maps:
+    grad_fmap1 = G x fmap2, grad_fmap2 = G^T x fmap1 (rocBLAS); None for the one nobody needs."""
+    B, _, H, W1 = f1.shape
+    G = gvol.view(B, H, W1, f2.shape[3])
+    gf1 = torch.einsum('bhwv,bchv->bchw', G, f2.float()) if need1 else None
+    gf2 = torch.einsum('bhwv,bchw->bchv', G, f1.float()) if need2 else None
+    return gf1, gf2
+
+
 class _BuildFn(torch.autograd.Function):
     """(fmap1, fmap2) -> pyramid levels.  Backward: avg-pool chain + 1/sqrt(C) folded by
     dkt_corr1d_pool_bwd, then grad_fmap1 = G x fmap2, grad_fmap2 = G^T x fmap1 (rocBLAS)."""
@@ -92,10 +102,7 @@ class _BuildFn(torch.autograd.Function):
                for i, g in enumerate(glv)]
         gvol = torch.empty((N, W2), device=f1.device, dtype=torch.float32)
         _ffi.call("dkt_corr1d_pool_bwd", gvol, _ffi.ptr_array(glv), gvol.data_ptr(), B, H, W1, W2, L, float(divisor))
-        G = gvol.view(B, H, W1, W2)
-        gf1 = torch.einsum('bhwv,bchv->bchw', G, f2.float()) if ctx.needs_input_grad[0] else None
-        gf2 = torch.einsum('bhwv,bchw->bchv', G, f1.float()) if ctx.needs_input_grad[1] else None
-        return gf1, gf2, None, None
+        return _volume_grads(gvol, f1, f2, ctx.needs_input_grad[0], ctx.needs_input_grad[1]) + (None, None)
 
 
 class _LookupFn(torch.autograd.Function):

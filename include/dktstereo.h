@@ -279,6 +279,32 @@ int dkt_pcv_lookup(const float *const *pyr, const float *coords, const float *si
                    int B, int G, int H, int W1, int W2, int L, int S, int factor,
                    int device, void *stream);
 
+/* Its backward: torch autograd through meta_arch/pcvnet/corr.py:33-51 and the grid_sample of pcvnet/utils/utils.py:59-74.
+ * sigma is differentiated as well as the pyramid: it is the previous iteration's head output and reaches the call with its
+ * graph (meta_arch/pcvnet/model.py:141 -> :122).  pyr (the values), coords, sigma as in the forward; grad_out (B, L*G*S, H, W1).
+ * Three results, each skipped when null (at least one is given):
+ *   grad_pyr  HOST array of L device pointers shaped like pyr, ZEROED (or holding earlier lookups' sums) by the caller:
+ *             grad_pyr[lv][n, fl] += g e, grad_pyr[lv][n, fl+1] += g w per tap in (g, s) order, zero-padding taps drop out;
+ *   gcoords, gsigma (B,G,H,W1), written in full: with d = g (v1m - v0m) / factor^lv, v0m and v1m the two taps after the
+ *             out-of-range one is zeroed, gcoords = sum d and gsigma = sum (s - S/2) d in ascending (level, s) order.
+ * Floors and weights are the forward's.  Deterministic: one owner per element, no atomics, no workspace; one launch for
+ * grad_pyr and one for gcoords / gsigma.  Errors: a null pointer the call needs or no result asked for DKT_E_NULL; B, G, H,
+ * W1, W2, S <= 0, S even, factor < 2 or B > 65535 DKT_E_SHAPE; L outside 1..DKT_MAX_LEVELS or a last level narrower than 2
+ * (the reference divides by W_i - 1) DKT_E_LEVELS. */
+int dkt_pcv_lookup_bwd(const float *const *pyr, const float *coords, const float *sigma, const float *grad_out,
+                       float *const *grad_pyr /* may be null */, float *gcoords /* may be null */,
+                       float *gsigma /* may be null */, int B, int G, int H, int W1, int W2, int L, int S, int factor,
+                       int device, void *stream);
+
+/* Folds the backward of the F.avg_pool2d(corr, [1,factor], stride=[1,factor]) chain of meta_arch/pcvnet/corr.py:29-31 and
+ * the 1/sqrt(D) of CorrBlock1D.corr (:61) into the gradient of the un-pooled all-pairs product: grad_vol (B*H*W1, W2) =
+ * T_0 / divisor with T_{L-1} = g_{L-1}, T_i[c] = g_i[c] + (c/factor < W_{i+1} ? T_{i+1}[c/factor] / factor : 0),
+ * W_{i+1} = W_i / factor (floor).  grad_pyr: HOST array of L device pointers, level i (B*H*W1, W_i).  Each element of
+ * grad_vol has one owner.  Errors as above, without the limit on B (the launch does not put it on the grid) and with
+ * DKT_E_SHAPE for a divisor that is not positive.  The two contractions that follow are those of dkt_corr1d_pool_bwd. */
+int dkt_pcv_pool_bwd(const float *const *grad_pyr, float *grad_vol, int B, int H, int W1, int W2,
+                     int L, int factor, float divisor, int device, void *stream);
+
 /* y = x / (||x||_2 over each of G contiguous channel groups + eps): the normalisation inside
  * groupwise_correlation_norm / norm_correlation, meta_arch/cgi/submodule.py:149,168 (eps 1e-5).
  * build_gwc_volume_norm(ref,tgt,D,G) = dkt_gwc_volume on the two normalised maps;
