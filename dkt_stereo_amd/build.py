@@ -58,9 +58,6 @@ def build(force=False, verbose=False):
             for tu in (0, 1, 2, 3, 4, 5, 6):
                 jobs.append((src, os.path.join(OBJ_DIR, "conv2d_tu%d.o" % tu), ["-DCONV_TU_PASSES=%d" % tu]))
         elif stem == "conv_c8":
-            old = os.path.join(OBJ_DIR, "conv_c8.o")       # (the single unit of earlier builds: the tools link every object here)
-            if os.path.exists(old):
-                os.remove(old)
             for tu in (3, 2, 1, 0):
                 jobs.append((src, os.path.join(OBJ_DIR, "conv_c8_tu%d.o" % tu), EXTRA_FLAGS[stem] + ["-DC8_TU=%d" % tu]))
         else:
@@ -83,6 +80,10 @@ def build(force=False, verbose=False):
         if res.returncode != 0:
             sys.stderr.write(res.stdout)
             raise RuntimeError("hipcc failed compiling %s %s" % (os.path.basename(src), " ".join(extra)))
+    # the tools link every object here: one whose source is gone (or is now compiled as several units) would give them
+    # duplicate symbols
+    for old in set(glob.glob(os.path.join(OBJ_DIR, "*.o"))) - {obj for _, obj, _ in jobs}:
+        os.remove(old)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + [obj for (_, obj, _), _ in results] + ["-o", LIB]
     if verbose:
         print(" ".join(cmd))

@@ -8,7 +8,7 @@
 //
 //   dkt_conv_grad_prepass   one streaming pass over gy [and y], then a one-block finish
 //
-// Shape of gru_gates_train.hip: float4 accesses when HW, the batch strides and the pointers allow it, 4-byte ones otherwise, a
+// Shape of the gate kernels (gru_gates.h): float4 accesses when HW, the batch strides and the pointers allow it, 4-byte ones otherwise, a
 // grid-stride loop over at most 2048 blocks of 256; every load of an item is issued before its first use.
 // The order of every sum is a function of the shape alone: a (batch, channel) plane is cut into segments of PRE_SEG elements,
 // a segment is one work item of one block (thread t owns the elements 4t..4t+3 of every 1024, added in ascending order; the 64
@@ -16,7 +16,7 @@
 // ascending (batch, segment).  No float atomics: the bias gradient is bit-identical from run to run, for every grid size and
 // for the 16-byte and the 4-byte path alike.  The maximum is taken on the bit patterns of |g'| (an unsigned maximum orders
 // finite < Inf < NaN), so a non-finite gradient is seen as such.
-#include "gru_gates.h"
+#include "dkt_common.h"
 #include "wave_reduce.h"
 
 #define PRE_SEG 4096          // elements per work item: 4 x float4 per thread

@@ -37,6 +37,9 @@ static inline int dkt_launch_status() {
     return e == hipSuccess ? DKT_OK : (int)e;
 }
 
+// (a null optional operand counts as aligned)
+static inline bool dkt_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+
 struct DktPtrs {
     const float *p[DKT_MAX_LEVELS];
 };

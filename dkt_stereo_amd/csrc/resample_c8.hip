@@ -1,8 +1,8 @@
 // resample_c8.hip -- pool2x / interp of the update block (core/update.py:87-95) writing the "C8S" operand of the next
 // convolution directly (conv_c8.hip): fp32 NCHW in, pre-split fp16 (hi, lo) [B][C/8][2][Hp][Wp][8] out.  Same arithmetic
-// and operation order as dkt_pool2x / dkt_interp_bilinear (norm.hip), i.e. ATen's; the split is the one of
-// dkt_act_c8_pack.  One thread = one output pixel x 8 channels (one 16-byte store per half).
-#include "dkt_common.h"
+// and operation order as dkt_pool2x / dkt_interp_bilinear (resample.hip), i.e. ATen's, through the helpers of resample.h;
+// the split is the one of dkt_act_c8_pack.  One thread = one output pixel x 8 channels (one 16-byte store per half).
+#include "resample.h"
 
 __device__ __forceinline__ unsigned rs_pack_h2(_Float16 a, _Float16 b) {
     union { _Float16 h[2]; unsigned u; } v;
@@ -36,58 +36,36 @@ __device__ __forceinline__ void pool2x_c8_body(const float *__restrict__ x, long
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int c = g * 8 + k;
-        const float *p = xb + (long)(c < C ? c : C - 1) * H * W;
         float t[9];
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const int iy = 2 * oy - 1 + dy;
-            const bool yok = iy >= 0 && iy < H;
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const int ix = 2 * ox - 1 + dx;
-                const bool ok = yok && ix >= 0 && ix < W;
-                const float u = p[(long)(yok ? iy : 0) * W + (ix >= 0 && ix < W ? ix : 0)];
-                t[dy * 3 + dx] = ok ? u : 0.0f;
-            }
-        }
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) s = __fadd_rn(s, t[i]);
-        v[k] = c < C ? __fdiv_rn(s, 9.0f) : 0.0f;
+        dkt_pool9_load(xb + (long)(c < C ? c : C - 1) * H * W, H, W, oy, ox, t);
+        const float avg = dkt_pool9_avg(t);
+        v[k] = c < C ? avg : 0.0f;
     }
     rs_store_c8(dst + (long)b * dst_bs + (long)((ch0 >> 3) + g) * 2 * plane + ((long)(oy + 1) * Wp + (ox + 1)) * 16, plane, v, scale);
 }
 
-// F.interpolate(x, (Ho, Wo), mode="bilinear", align_corners=True) in ATen's order (see interp_kernel, norm.hip)
+// F.interpolate(x, (Ho, Wo), mode="bilinear", align_corners=True) in ATen's order (dkt_lerp, resample.h)
 __device__ __forceinline__ void interp_c8_body(const float *__restrict__ x, long x_bs, char *__restrict__ dst, long dst_bs,
                                                int C, int H, int W, int Ho, int Wo, float sy, float sx, int Wp, long plane,
                                                int ch0, float scale, int bx, int oy, int bz) {
     const int ox = bx * 128 + threadIdx.x;
     const int g = bz % ((C + 7) / 8), b = bz / ((C + 7) / 8);
     if (ox >= Wo) return;
-    const float fy = __fmul_rn(sy, (float)oy);
-    const int y0 = (int)fy;
-    const int y1 = y0 + (y0 < H - 1 ? 1 : 0);
-    const float ly1 = __fsub_rn(fy, (float)y0), ly0 = __fsub_rn(1.0f, ly1);
-    const float fx = __fmul_rn(sx, (float)ox);
-    const int x0 = (int)fx;
-    const int x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float lx1 = __fsub_rn(fx, (float)x0), lx0 = __fsub_rn(1.0f, lx1);
+    const DktLerp ty = dkt_lerp(oy, sy, H), tx = dkt_lerp(ox, sx, W);
     const float *xb = x + (long)b * x_bs;
     float a0[8], a1[8], b0[8], b1[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int c = g * 8 + k;
         const float *p = xb + (long)(c < C ? c : C - 1) * H * W;
-        a0[k] = p[(long)y0 * W + x0]; a1[k] = p[(long)y0 * W + x1];
-        b0[k] = p[(long)y1 * W + x0]; b1[k] = p[(long)y1 * W + x1];
+        a0[k] = p[(long)ty.i0 * W + tx.i0]; a1[k] = p[(long)ty.i0 * W + tx.i1];
+        b0[k] = p[(long)ty.i1 * W + tx.i0]; b1[k] = p[(long)ty.i1 * W + tx.i1];
     }
     float v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const float top = __fadd_rn(__fmul_rn(lx0, a0[k]), __fmul_rn(lx1, a1[k]));
-        const float bot = __fadd_rn(__fmul_rn(lx0, b0[k]), __fmul_rn(lx1, b1[k]));
-        v[k] = g * 8 + k < C ? __fadd_rn(__fmul_rn(ly0, top), __fmul_rn(ly1, bot)) : 0.0f;
+        const float o = dkt_lerp_blend(ty, tx, a0[k], a1[k], b0[k], b1[k]);
+        v[k] = g * 8 + k < C ? o : 0.0f;
     }
     rs_store_c8(dst + (long)b * dst_bs + (long)((ch0 >> 3) + g) * 2 * plane + ((long)(oy + 1) * Wp + (ox + 1)) * 16, plane, v, scale);
 }
