@@ -218,6 +218,8 @@ SIGNATURES = {
     "dkt_pcv_lookup": [_pp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_pcv_lookup_bwd": [_pp, _vp, _vp, _vp, _pp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "dkt_pcv_pool_bwd": [_pp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
+    "dkt_pcv_update_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp],
+    "dkt_pcv_update_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp],
     "dkt_group_l2norm": [_vp, _vp, _i, _i, _l, _i, ctypes.c_float, _i, _vp],
     "dkt_corr1d_skew_pitch": [_i],
     "dkt_corr1d_skew": [_pp, _pp, _i, _i, _i, _i, _i, _i, _vp],

@@ -305,6 +305,49 @@ int dkt_pcv_lookup_bwd(const float *const *pyr, const float *coords, const float
 int dkt_pcv_pool_bwd(const float *const *grad_pyr, float *grad_vol, int B, int H, int W1, int W2,
                      int L, int factor, float divisor, int device, void *stream);
 
+/* PCVNet's mixture-parameter update: ParametersUpdater.forward after its conv head (meta_arch/pcvnet/update.py:92-107) and
+ * the disparity regression of meta_arch/pcvnet/model.py:154, in one launch.  delta (the head's output), mu, sigma, w and the
+ * three results (N,M,H,W) contiguous, M = gauss_num; per pixel, j over the M gaussians:
+ *   ds_raw = 0.5 (((1 - M w) sigma^2 - sigma0^2 - delta^2) / (M sigma^3) + w sigma / sigma0^2)
+ *   dm_raw = -0.5 delta (1 / (M sigma^2) + w / sigma0^2)
+ *   beta   = 0.5 (-1 / (M w + eps) + log(sigma0 M w / sigma + eps) + (sigma^2 + delta^2) / (2 sigma0^2) + 0.5)
+ *   dw_raw = beta - (sum_j beta) / M
+ *   ds = clip(gamma1 ds_raw, +-3)   dm = clip(gamma2 dm_raw, +-128)   dw = clip(gamma3 dw_raw, +-1/(4M))
+ *   sigma_out = clip(sigma - ds, 0.1, 16)   mu_out = mu - dm   w~ = clip(w - dw, 0, 1)   w_out = w~ / sum_j w~
+ *   disp (N,1,H,W) = sum_j w_out mu_out                              (skipped when null)
+ * code (N,M,H,W) bytes, skipped when null: the five three-state clip decisions of an element (0 below, 1 inside or on an
+ * edge, 2 above) as (((ds 3 + dm) 3 + dw) 3 + sigma_out) 3 + w~, at most 242: all the backward needs beside the four inputs.
+ * One thread per pixel (four adjacent ones as 16-byte accesses when H*W is a multiple of 4 and every pointer is 16-byte
+ * aligned), sums in ascending j, IEEE division and logf: the same bits every run.  A pixel whose w~ are all zero is NaN in
+ * w_out and disp, as in the reference.
+ * Errors (both entries, before any device call): a null pointer the call needs DKT_E_NULL; N, M, H, W <= 0 DKT_E_SHAPE;
+ * M > 8, N > 65535 or H*W > 2^31 - 257 DKT_E_UNSUPPORTED. */
+int dkt_pcv_update_fwd(const float *delta, const float *mu, const float *sigma, const float *w,
+                       float *mu_out, float *w_out, float *sigma_out, float *disp /* may be null */,
+                       unsigned char *code /* may be null */, int N, int M, int H, int W,
+                       float sigma0, float eps, float gamma1, float gamma2, float gamma3, int device, void *stream);
+
+/* Its backward (torch autograd through update.py:92-107 and model.py:154), one launch.  The four inputs and code as the
+ * forward read and wrote them; upstream gradients gmu_out, gw_out, gsigma_out (N,M,H,W) and gdisp (N,1,H,W), a null one
+ * standing for zeros; results gdelta, gmu, gsigma, gw (N,M,H,W), a null one not computed.  All four upstream gradients
+ * null, or all four results null, is DKT_E_NULL.  beta, dm_raw, w~ and w_out are recomputed from the inputs by the
+ * forward's own functions with the decisions replayed from code; a clip passes its gradient where the value was inside or
+ * on the edge (torch.clamp's backward).  With T = sum_j w~, u = sigma0 M w / sigma + eps and c the pass indicators:
+ *   Gmu = gmu_out + gdisp w_out   Gw = gw_out + gdisp mu_out   A = c_w~ (Gw - sum_k Gw_k w_out_k) / T   B = -gamma3 c_dw A
+ *   gbeta = B - (sum_k B_k) / M   E = c_sigma gsigma_out   g_ds = -gamma1 c_ds E   g_dm = -gamma2 c_dm Gmu
+ *   gdelta = g_ds (-delta / (M sigma^3)) + g_dm (-0.5 (1 / (M sigma^2) + w / sigma0^2)) + gbeta delta / (2 sigma0^2)
+ *   gsigma = E + g_ds 0.5 (-(1 - M w) / (M sigma^2) + 3 (sigma0^2 + delta^2) / (M sigma^4) + w / sigma0^2)
+ *            + g_dm delta / (M sigma^3) + gbeta 0.5 (-(sigma0 M w / sigma^2) / u + sigma / sigma0^2)
+ *   gw = A + g_ds 0.5 (-1 / sigma + sigma / sigma0^2) + g_dm (-0.5 delta / sigma0^2)
+ *        + gbeta 0.5 (M / (M w + eps)^2 + (sigma0 M / sigma) / u),            gmu = Gmu.
+ * Deterministic: one owner per element, no atomics, no workspace. */
+int dkt_pcv_update_bwd(const float *delta, const float *mu, const float *sigma, const float *w, const unsigned char *code,
+                       const float *gmu_out /* may be null */, const float *gw_out /* may be null */,
+                       const float *gsigma_out /* may be null */, const float *gdisp /* may be null */,
+                       float *gdelta /* may be null */, float *gmu /* may be null */, float *gsigma /* may be null */,
+                       float *gw /* may be null */, int N, int M, int H, int W,
+                       float sigma0, float eps, float gamma1, float gamma2, float gamma3, int device, void *stream);
+
 /* y = x / (||x||_2 over each of G contiguous channel groups + eps): the normalisation inside
  * groupwise_correlation_norm / norm_correlation, meta_arch/cgi/submodule.py:149,168 (eps 1e-5).
  * build_gwc_volume_norm(ref,tgt,D,G) = dkt_gwc_volume on the two normalised maps;
