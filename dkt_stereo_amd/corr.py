@@ -344,6 +344,8 @@ class PytorchAlternateCorrBlock1D:
         # right feature map pooled along W once per level (corr.py:104 does it per call)
         self._f2pyr = [self.fmap2]
         B, C, H, W2 = self.fmap2.shape
+        if self.fmap1.dim() != 4 or tuple(self.fmap1.shape[:3]) != (B, C, H):
+            raise ValueError("fmap1 %s and fmap2 %s disagree" % (tuple(self.fmap1.shape), tuple(self.fmap2.shape)))
         for i in range(1, num_levels):
             src = self._f2pyr[-1]
             dst = torch.empty((B, C, H, src.shape[3] // 2), device=src.device, dtype=torch.float32)
@@ -354,6 +356,8 @@ class PytorchAlternateCorrBlock1D:
         _ffi.require_gpu(coords)
         coords = coords.contiguous()
         B, C, H, W1 = self.fmap1.shape
+        if tuple(coords.shape) != (B, 2, H, W1):
+            raise ValueError("coords %s, expected %s" % (tuple(coords.shape), (B, 2, H, W1)))
         W2 = self.fmap2.shape[3]
         K = 2 * self.radius + 1
         out = torch.empty((B, self.num_levels * K, H, W1), device=coords.device, dtype=torch.float32)

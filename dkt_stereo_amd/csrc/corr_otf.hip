@@ -118,7 +118,9 @@ __global__ __launch_bounds__(256) void corr1d_otf_kernel(OtfArgs a) {
 #pragma unroll
         for (int pass = 0; pass < 2; ++pass) {
             const int row = y0 + pass;                               // block-uniform
-            if (!(need & (1 << pass)) || row < 0 || row >= a.H) continue;
+            // an empty window (every tap of every pixel outside the row: lo is still its initial INT_MAX) stages
+            // nothing -- the row pointer below would lie 8 GiB past the level -- and D stays 0
+            if (ncol == 0 || !(need & (1 << pass)) || row < 0 || row >= a.H) continue;
             // ---- wave w walks its channel quarter in groups of OTF_CG channels: stage the group's window
             // (lane = column; 16 row reads in flight), then each half-wave dots half of the group.  The
             // group buffer is wave-private (program order suffices: no barrier) and small (8 KB per wave),
