@@ -159,6 +159,34 @@ class NsLossGrad(ctypes.Structure):
     """dkt_ns_loss_grad of include/dktstereo.h."""
     _fields_ = [("grad", ctypes.c_void_p * NS_MAX_PRED), ("grad_loss", ctypes.c_void_p)]
 
+
+#: DKT_PCV_LOSS_MAX_PRED, DKT_PCV_LOSS_MAX_M, DKT_PCV_LOSS_REC of include/dktstereo.h
+PCV_LOSS_MAX_PRED, PCV_LOSS_MAX_M, PCV_LOSS_REC = 7, 8, 40
+
+
+class PcvLossDesc(ctypes.Structure):
+    """dkt_pcv_loss_desc of include/dktstereo.h."""
+    _fields_ = [("disp", ctypes.c_void_p * PCV_LOSS_MAX_PRED), ("disp_bstride", ctypes.c_long * PCV_LOSS_MAX_PRED),
+                ("mu", ctypes.c_void_p * PCV_LOSS_MAX_PRED), ("mu_bstride", ctypes.c_long * PCV_LOSS_MAX_PRED),
+                ("mu_gstride", ctypes.c_long * PCV_LOSS_MAX_PRED),
+                ("w", ctypes.c_void_p * PCV_LOSS_MAX_PRED), ("w_bstride", ctypes.c_long * PCV_LOSS_MAX_PRED),
+                ("w_gstride", ctypes.c_long * PCV_LOSS_MAX_PRED),
+                ("sigma", ctypes.c_void_p * PCV_LOSS_MAX_PRED), ("sigma_bstride", ctypes.c_long * PCV_LOSS_MAX_PRED),
+                ("sigma_gstride", ctypes.c_long * PCV_LOSS_MAX_PRED),
+                ("weight", ctypes.c_float * PCV_LOSS_MAX_PRED),
+                ("refine", ctypes.c_void_p), ("refine_bstride", ctypes.c_long), ("refine_weight", ctypes.c_float),
+                ("n", ctypes.c_int), ("n_loss", ctypes.c_int), ("M", ctypes.c_int), ("ntargets", ctypes.c_int),
+                ("gt", ctypes.c_void_p * 2), ("gt_bstride", ctypes.c_long * 2),
+                ("valid", ctypes.c_void_p * 2), ("valid_bstride", ctypes.c_long * 2), ("max_disp", ctypes.c_float),
+                ("mask", ctypes.c_void_p * 2), ("loss", ctypes.c_void_p * 2), ("rec", ctypes.c_void_p),
+                ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int)]
+
+
+class PcvLossGrad(ctypes.Structure):
+    """dkt_pcv_loss_grad of include/dktstereo.h."""
+    _fields_ = [("gdisp", ctypes.c_void_p * PCV_LOSS_MAX_PRED), ("gmu", ctypes.c_void_p * PCV_LOSS_MAX_PRED),
+                ("grefine", ctypes.c_void_p), ("grad_loss", ctypes.c_void_p * 2)]
+
 # name -> argtypes, mirrors include/dktstereo.h one to one
 SIGNATURES = {
     "dkt_loop_status": [ctypes.POINTER(C8RangeJob), _i, _vp, _l, _vp, _vp, _i, _vp],
@@ -169,6 +197,9 @@ SIGNATURES = {
     "dkt_ns_loss_workspace": [_i, _i, _i],
     "dkt_ns_loss": [ctypes.POINTER(NsLossDesc), _vp, _i, _vp],
     "dkt_ns_loss_bwd": [ctypes.POINTER(NsLossDesc), ctypes.POINTER(NsLossGrad), _i, _vp],
+    "dkt_pcv_loss_partial_doubles": [_i, _i, _i, _i],
+    "dkt_pcv_loss": [ctypes.POINTER(PcvLossDesc), _vp, _i, _vp],
+    "dkt_pcv_loss_bwd": [ctypes.POINTER(PcvLossDesc), ctypes.POINTER(PcvLossGrad), _i, _vp],
     "dkt_motion_front_c8": [ctypes.POINTER(MotionFrontDesc), _i, _vp],
     "dkt_resample_pair_c8": [ctypes.POINTER(ResampleC8Job), ctypes.POINTER(ResampleC8Job), _i, _vp],
     "dkt_gru_c8_flag_words": [_i, _i, _i],
@@ -278,7 +309,7 @@ SIGNATURES = {
     "dkt_interp_bilinear_bwd": [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp],
 }
 #: entry points that do not return an int status
-RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long, "dkt_adamw_workspace": ctypes.c_long, "dkt_soft_argmin_bwd_workspace": ctypes.c_long, "dkt_ns_loss_workspace": ctypes.c_long}
+RESTYPES = {"dkt_gru_c8_flag_words": ctypes.c_long, "dkt_seq_loss_ws_doubles": ctypes.c_long, "dkt_conv2d_stats_ws_floats": ctypes.c_long, "dkt_conv_grad_prepass_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad_s2_ws_floats": ctypes.c_long, "dkt_conv2d_wgrad7_ws_floats": ctypes.c_long, "dkt_conv_c8_packed_bytes": ctypes.c_long, "dkt_conv2d_packed_elems": ctypes.c_long, "dkt_conv2d_stem7_packed_elems": ctypes.c_long, "dkt_instance_norm_workspace": ctypes.c_long, "dkt_instance_norm_bwd_workspace": ctypes.c_long, "dkt_adamw_workspace": ctypes.c_long, "dkt_soft_argmin_bwd_workspace": ctypes.c_long, "dkt_ns_loss_workspace": ctypes.c_long, "dkt_pcv_loss_partial_doubles": ctypes.c_long}
 
 #: DKT_E_UNSUPPORTED of include/dktstereo.h
 E_UNSUPPORTED = -7

@@ -1169,6 +1169,68 @@ long dkt_ns_loss_workspace(int B, int H, int W);
 int dkt_ns_loss(const dkt_ns_loss_desc *d, void *ws, int device, void *stream);
 int dkt_ns_loss_bwd(const dkt_ns_loss_desc *d, const dkt_ns_loss_grad *g, int device, void *stream);
 
+/* ---- PCVNet sequence loss (csrc/pcv_loss.hip) ---------------------------------------------------------------------------
+ * Replaces sequence_loss_pcvnet (meta_arch/pcvnet/loss.py:4-73) for one or two targets against the same predictions
+ * (tools/ft_dkt.py:227-228 calls the loss twice).  n predictions, each final_disp_i (B,1,H,W) and mu_i, w_i, sigma_i of M
+ * gaussians; disp_refine (B,1,H,W).  Per target k:
+ *   mask_k = (gt < max_disp) & (valid != 0) & (gt >= 0), written as bool (B,1,H,W) contiguous (valid NaN counts as set; a
+ *   NaN or +-Inf gt is off the mask, so loss.py:17 cannot fire);  N_k = its count;
+ *   mean1_i = mean over the mask of |fl32(disp_i - gt)|;  mean2_i = mean over the mask of fl32(fl32(sum_m |fl32(mu_i,m - gt)|) / M);
+ *   sl1 = mean over the mask of smooth-L1 (beta = 1) of disp_refine - gt;
+ *   loss_k = sum_{i < n_loss} weight[i] * (mean1_i + mean2_i) + refine_weight * sl1, accumulated in fp32 in that order
+ *   (weight[i], refine_weight already fp32).  The mean of an empty set is NaN, as torch's is.
+ * Sums are fp64 per-block partials reduced in a fixed order by a finalize launch: bit-identical from run to run, no atomics.
+ * rec (DKT_PCV_LOSS_REC doubles), written by the finalize launch:
+ *   rec[16k + 0] = N_k;  rec[16k + 1 .. 7] = of final_disp 3 over the mask (0 when n < 4): the fl32 EPE mean, then the fl32
+ *   fractions of EPE < 1, < 3, < 5, > 1, > 2, > 5 (all strict, on |fl32(p - gt)|);  rec[16k + 8 .. 14] = the same of disp_refine;
+ *   rec[32] = the flag word: bit i set when mu_i, w_i, sigma_i or final_disp_i holds a NaN or an Inf anywhere, on or off the
+ *   mask (loss.py:30-33).  disp_refine has no flag: its NaN goes into the loss.
+ * disp[i], refine, gt, valid: contiguous H x W planes with a batch stride; mu[i], w[i], sigma[i]: plane (b, m) at
+ * b * bstride + m * gstride, so (B M,1,H,W), (B,M,1,H,W) and [:, :1] views are read in place.  w[i] / sigma[i] may be null:
+ * that tensor is then not read (they enter through the finite check only).  ws: dkt_pcv_loss_partial_doubles(ntargets, B, H, W)
+ * doubles.  Accesses are 16 bytes when H W % 4 == 0 and every pointer and stride allows it, scalar otherwise.
+ * Two launches (partials, finalize); no host synchronisation.
+ * Errors (every entry, before any device call): null desc / ws / a pointer the call needs DKT_E_NULL; B, H, W <= 0, n outside
+ * 1..DKT_PCV_LOSS_MAX_PRED, n_loss outside 1..min(n, 6), M outside 1..DKT_PCV_LOSS_MAX_M or ntargets outside 1..2
+ * DKT_E_SHAPE; H*W > 2^31 - 1025 or B > 65535 DKT_E_UNSUPPORTED.  dkt_pcv_loss_partial_doubles returns DKT_E_SHAPE for ntargets
+ * outside 1..2 or B, H, W <= 0. */
+#define DKT_PCV_LOSS_MAX_PRED 7
+#define DKT_PCV_LOSS_MAX_M 8
+#define DKT_PCV_LOSS_REC 40
+typedef struct dkt_pcv_loss_desc {
+    const float *disp[DKT_PCV_LOSS_MAX_PRED]; long disp_bstride[DKT_PCV_LOSS_MAX_PRED];
+    const float *mu[DKT_PCV_LOSS_MAX_PRED]; long mu_bstride[DKT_PCV_LOSS_MAX_PRED], mu_gstride[DKT_PCV_LOSS_MAX_PRED];
+    const float *w[DKT_PCV_LOSS_MAX_PRED]; long w_bstride[DKT_PCV_LOSS_MAX_PRED], w_gstride[DKT_PCV_LOSS_MAX_PRED];
+    const float *sigma[DKT_PCV_LOSS_MAX_PRED]; long sigma_bstride[DKT_PCV_LOSS_MAX_PRED], sigma_gstride[DKT_PCV_LOSS_MAX_PRED];
+    float weight[DKT_PCV_LOSS_MAX_PRED];
+    const float *refine; long refine_bstride;
+    float refine_weight;
+    int n, n_loss, M, ntargets;
+    const float *gt[2]; long gt_bstride[2];
+    const float *valid[2]; long valid_bstride[2];
+    float max_disp;
+    unsigned char *mask[2];                     /* out */
+    float *loss[2];                             /* out, device scalars */
+    double *rec;                                /* out */
+    int B, H, W;
+} dkt_pcv_loss_desc;
+long dkt_pcv_loss_partial_doubles(int ntargets, int B, int H, int W);
+int dkt_pcv_loss(const dkt_pcv_loss_desc *d, double *ws, int device, void *stream);
+/* Backward of dkt_pcv_loss in ONE launch, after it on the same stream, reading its masks and rec on the device.  On mask_k,
+ * with g_k = *grad_loss[k] (device scalars) and q_i,k = fl(fl(g_k * weight[i]) / N_k):
+ *   gdisp[i] = sum_k q_i,k * sgn(disp_i - gt_k)            gmu[i] = sum_k fl(q_i,k / M) * sgn(mu_i,m - gt_k)      (sgn(0) = 0)
+ *   grefine  = sum_k smooth-L1 backward with norm fl32(1 / N_k) and upstream fl(g_k * refine_weight)
+ * and exactly 0 off every mask and for i >= n_loss.  A target with N_k = 0 or a null grad_loss[k] contributes exactly 0.
+ * gdisp[i], grefine: (B,1,H,W) contiguous; gmu[i]: (B,M,H,W) contiguous; a null one is not required and is skipped; every
+ * element of the others is stored once.  w and sigma have no gradient.  Errors as dkt_pcv_loss, plus a null g DKT_E_NULL. */
+typedef struct dkt_pcv_loss_grad {
+    float *gdisp[DKT_PCV_LOSS_MAX_PRED];
+    float *gmu[DKT_PCV_LOSS_MAX_PRED];
+    float *grefine;
+    const float *grad_loss[2];
+} dkt_pcv_loss_grad;
+int dkt_pcv_loss_bwd(const dkt_pcv_loss_desc *d, const dkt_pcv_loss_grad *g, int device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
